@@ -11,15 +11,22 @@ when --gpus > 1).  One JSON line is printed by rank 0 (contract in the task desc
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 8                       # launches 8 ranks itself (torch.distributed.run, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                # + everything below
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    # + the last timed step's outputs as DIR/<name>.npy
 
-The other BASELINE configurations are timed as `extra_workloads` of the same line, each with its own roofline object:
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the line (with the QP kernel's
+roofline from the timed region's own events).  Everything else runs only with --full: the durations of the linearisation and
+line-search kernels (a pass of their own behind the timed region: `kernel_ms`, `roofline_linearize`), the other workloads
+(`extra_workloads`) and the CPU baseline (`cpu_baseline`).
+
+With --full the other BASELINE configurations are timed as `extra_workloads` of the same line, each with its own roofline object:
 configs[2] (Thing + 3 stacked objects + static obstacles, batch 4096; N = 1 only), configs[3] (upright_robust 8-corner
 arrangement with per-instance inertial parameters, 1024 per GPU: with --gpus N the N x 1024 scenarios are sharded over the
 ranks and the solved trajectories all-gathered), configs[4] (thrown ball, closed loop at 100 Hz: the goal sweep is sharded
 over the ranks and only the first input u_0 of every instance is gathered per tick), and the headline problem on the start
 distribution of SURVEY.md section 8(d) as written (U(+-0.25) on all nine joints; N = 1 only).
 
-    python bench.py --gpus 2 --dry-run             # the N-rank control flow over gloo with stand-in engines (no GPU, no numbers)
+    python bench.py --gpus 2 --dry-run --full      # the N-rank control flow over gloo with stand-in engines (no GPU, no numbers)
 """
 import argparse
 import json
@@ -853,21 +860,59 @@ def _strip(e):
     return e
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: every file together
+DUMP_GAINS = 64             # instances whose feedback gains are written (90 KB each at the headline's shape)
+
+
+def dump_outputs(out_dir, mpc):
+    """--dump-outputs DIR: what the timed path computed in its last step, as a caller of the engine receives it, one float64
+    DIR/<name>.npy per array: the plan (`ts`, `xs`, `us` of BatchMPC.solution), every per-instance statistic (`stats_<name>`)
+    and, with the feedback policy on, the gains K of a fixed seeded sample of instances (`feedback_gains`, their indices in
+    `feedback_gains_instances`).  The inputs are seeded, so two builds run with the same arguments compare file for file.
+    Should the per-instance arrays pass the 64 MB budget (a larger --batch), a fixed seeded sample of instances is written
+    instead, its indices in `instances`.  With --gpus N: rank 0's instances."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    ts, xs, us = mpc.solution()
+    arrays = {"ts": ts, "xs": xs, "us": us}
+    arrays.update({"stats_" + k: v for k, v in mpc.stats().items()})
+    B = xs.shape[0]
+    gains = {}
+    if mpc.problem.use_feedback_policy:
+        kidx = np.sort(np.random.default_rng(0).choice(B, min(B, DUMP_GAINS), replace=False))
+        gains = {"feedback_gains": mpc.feedback_gains()[kidx], "feedback_gains_instances": kidx}
+    per_inst = sum(a[0].nbytes for a in arrays.values())
+    room = DUMP_BYTES - sum(a.nbytes for a in gains.values()) - 8 * B
+    if per_inst * B > room:
+        idx = np.sort(np.random.default_rng(1).choice(B, room // per_inst, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["instances"] = idx
+    arrays.update(gains)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="instances per GPU")
-    ap.add_argument("--cpu-sample", type=int, default=1024, help="instances of the CPU-baseline sample (rank 0, N=1): ~11 core-seconds at the default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configurations (configs[2], configs[3], configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel pass (kernel_ms, roofline_linearize), the other BASELINE configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (plans, statistics, a sample of the feedback gains) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=1024, help="instances of the CPU-baseline sample (rank 0, N=1, --full): ~11 core-seconds at the default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the other BASELINE configurations (configs[2], configs[3], configs[4])")
     ap.add_argument("--extra-steps", type=int, default=3)
     ap.add_argument("--closed-loop-ticks", type=int, default=150, help="control periods of the configs[4] closed-loop run")
     ap.add_argument("--only", default=None, choices=["config3", "config4", "config5", "config5s", "contract", "headline_r03", "config4_horizon"],
                     help="run ONE of the other workloads alone and print its entry (the per-workload counter passes of tools/profile_all.sh)")
     ap.add_argument("--dry-run", action="store_true", help="control flow only: gloo on the CPU, stand-in engines with fake solutions; prints a line marked dry_run (never a measurement)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry_run or args.only):
+        raise SystemExit("bench.py: --dump-outputs writes the headline solve's outputs; --dry-run and --only have none")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args))
@@ -940,15 +985,17 @@ def main():
         assert gathered[0].shape[0] == world * B and bool(torch.isfinite(gathered[0]).all())
     kt = mpc.kernel_times()
     st = mpc.stats()
-    if not dry:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mpc)
+    if args.full and not dry:
         kt = aux_kernel_times(mpc, kt)
     mpc.enable_timing(False)
     mpc.close()
 
-    # the other BASELINE configurations: every rank takes part in the sharded ones (configs[3], configs[4]); rank 0 alone
+    # the other BASELINE configurations (--full): every rank takes part in the sharded ones (configs[3], configs[4]); rank 0 alone
     # prints.  configs[2] and the SURVEY start distribution are single-GPU workloads (N = 1 only).
     extra = []
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         if world == 1 and not dry:
             extra.append(time_extra(config3_workload(4096), args.extra_steps, 1, warm=(9, 3)))
         w4 = config4_workload(args.batch if dry else 1024, rank, world)
@@ -993,20 +1040,22 @@ def main():
                 "qp_iters_mean": float(np.mean(st["qp_iters_last"])),
             },
             "roofline": roof,
-            "roofline_linearize": lin,
-            "kernel_ms": {"linearize": kt["linearize_ms"], "qp": kt["qp_ms"], "linesearch": kt["linesearch_ms"], "launches": kt["launches"],
-                          "source": "qp: HIP events on the engine's stream around every fourth QP launch of the timed region (launches[1] of them); linearize, linesearch: "
-                                    "10 more solves of the same batch behind the region with events around every kernel (qp there: "
-                                    f"{kt.get('aux_qp_ms', 0.0):.4f} ms)"},
             "rank_devices": rank_devices,      # HIP device index of every engine each rank created (rank r: [LOCAL_RANK r])
         }
+        if args.full:
+            # (the linearisation and line-search durations come from the pass of their own behind the timed region)
+            out["roofline_linearize"] = lin
+            out["kernel_ms"] = {"linearize": kt["linearize_ms"], "qp": kt["qp_ms"], "linesearch": kt["linesearch_ms"], "launches": kt["launches"],
+                                "source": "qp: HIP events on the engine's stream around every fourth QP launch of the timed region (launches[1] of them); linearize, linesearch: "
+                                          "10 more solves of the same batch behind the region with events around every kernel (qp there: "
+                                          f"{kt.get('aux_qp_ms', 0.0):.4f} ms)"}
         if dry:
             out["dry_run"] = True
             out["value"] = 0.0; out["ms_per_step"] = 0.0; out["ms_per_sqp_iter"] = 0.0
             out["data"] = "none: --dry-run exercises the control flow with stand-in engines; no number of this line is a measurement"
         if extra:
             out["extra_workloads"] = extra
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(w, args.cpu_sample)
         print(json.dumps(out))
     if world > 1:

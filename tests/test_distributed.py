@@ -173,7 +173,7 @@ def test_bench_extra_workloads_two_ranks():
 
 
 def test_bench_dry_run_two_ranks():
-    """`python bench.py --gpus 2 --dry-run`: bench.py launches its two ranks itself, runs the headline loop and both sharded
+    """`python bench.py --gpus 2 --dry-run --full`: bench.py launches its two ranks itself, runs the headline loop and both sharded
     extra workloads over gloo with stand-in engines and exits 0 with one line that says it is not a measurement."""
     import json
     import subprocess
@@ -181,7 +181,7 @@ def test_bench_dry_run_two_ranks():
     from pathlib import Path
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, str(Path(__file__).resolve().parents[1] / "bench.py"), "--gpus", "2", "--dry-run", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, str(Path(__file__).resolve().parents[1] / "bench.py"), "--gpus", "2", "--dry-run", "--full", "--no-cpu-baseline",
                         "--batch", "5", "--steps", "2", "--warmup", "1", "--closed-loop-ticks", "2", "--extra-steps", "1"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -195,7 +195,7 @@ def test_bench_dry_run_two_ranks():
 
 
 def test_bench_dry_run_eight_ranks():
-    """`python bench.py --gpus 8 --dry-run --batch 1024`: the shape of the driver's 8-GPU run (8 x 1024 = BASELINE's 8192 upright_robust
+    """`python bench.py --gpus 8 --dry-run --full --batch 1024`: the shape of the driver's 8-GPU run (8 x 1024 = BASELINE's 8192 upright_robust
     scenarios, 8192 goals of the thrown-ball sweep) over gloo with stand-in engines.  Every rank creates its engines for device
     LOCAL_RANK = 0 ... 7; the gathered trajectories / first inputs have 8192 rows on rank 0."""
     import json
@@ -204,7 +204,7 @@ def test_bench_dry_run_eight_ranks():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     t0 = time.time()
-    r = subprocess.run([sys.executable, str(Path(__file__).resolve().parents[1] / "bench.py"), "--gpus", "8", "--dry-run", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, str(Path(__file__).resolve().parents[1] / "bench.py"), "--gpus", "8", "--dry-run", "--full", "--no-cpu-baseline",
                         "--batch", "1024", "--steps", "2", "--warmup", "1", "--closed-loop-ticks", "2", "--extra-steps", "1"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -215,6 +215,69 @@ def test_bench_dry_run_eight_ranks():
     assert e3["n_gpus"] == 8 and e4["n_gpus"] == 8
     assert e3["gathered_rows"] == 8192 and e4["gathered_rows"] == 8192
     assert time.time() - t0 < 120
+
+
+def test_bench_plain_dry_run_is_the_headline_only():
+    """Without --full the line holds the headline alone: no other workload, no CPU baseline, no per-kernel pass."""
+    import json
+    import subprocess
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, str(Path(__file__).resolve().parents[1] / "bench.py"), "--gpus", "2", "--dry-run",
+                        "--batch", "5", "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["dry_run"] is True and out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    for k in ("extra_workloads", "cpu_baseline", "kernel_ms", "roofline_linearize"):
+        assert k not in out
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the engine's arrays as float64 .npy files, at most 64 MB together; past that a fixed seeded sample of
+    instances (the same one in every run), and the feedback gains of a fixed sample of at most 64 instances."""
+    import types
+
+    import bench
+
+    class Eng:
+        def __init__(self, B, N=20, nx=27, nu=21):
+            self.problem = types.SimpleNamespace(use_feedback_policy=True)
+            i = np.arange(B, dtype=np.float64)
+            self.ts = np.tile(np.arange(N + 1) * 0.1, (B, 1))
+            self.xs = np.broadcast_to(i[:, None, None], (B, N + 1, nx)).copy()
+            self.us = -np.broadcast_to(i[:, None, None], (B, N, nu)).copy()
+            self.K = np.broadcast_to(i[:, None, None, None], (B, N, nu, nx)).copy()
+
+        def solution(self):
+            return self.ts, self.xs, self.us
+
+        def stats(self):
+            return {"qp_status_last": np.zeros(len(self.xs)), "qp_iters_last": np.arange(len(self.xs), dtype=np.float64)}
+
+        def feedback_gains(self):
+            return self.K
+
+    small = Eng(100)
+    bench.dump_outputs(tmp_path / "small", small)
+    names = {p.stem for p in (tmp_path / "small").iterdir()}
+    assert names == {"ts", "xs", "us", "stats_qp_status_last", "stats_qp_iters_last", "feedback_gains", "feedback_gains_instances"}
+    xs = np.load(tmp_path / "small" / "xs.npy")
+    assert xs.dtype == np.float64 and np.array_equal(xs, small.xs)
+    kidx = np.load(tmp_path / "small" / "feedback_gains_instances.npy").astype(int)
+    assert len(kidx) == 64 and np.array_equal(np.load(tmp_path / "small" / "feedback_gains.npy"), small.K[kidx])
+
+    big = Eng(9000)      # 9000 x 8.3 KB of plan and statistics: past the budget
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, big)
+    files = list((tmp_path / "a").iterdir())
+    assert sum(p.stat().st_size for p in files) <= 64 * 2 ** 20
+    idx = np.load(tmp_path / "a" / "instances.npy").astype(int)
+    assert 0 < len(idx) < 9000 and np.array_equal(idx, np.load(tmp_path / "b" / "instances.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "us.npy"), big.us[idx])
+    for p in files:
+        assert np.array_equal(np.load(p), np.load(tmp_path / "b" / p.name))
 
 
 def _ragged_worker(rank, world, port, total, q):

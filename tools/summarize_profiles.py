@@ -43,7 +43,7 @@ if len(sys.argv) > 2 and sys.argv[2] == "all":
         for k, v in acc.items():
             rows.append((k, counter, len(v), sum(v) / len(v)))
     with open(f"{out}/{tag}_pmc_hbm_all.csv", "w") as fh:
-        fh.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py --steps 2 --warmup 1 --extra-steps 2 --closed-loop-ticks 20 (all workloads)\n")
+        fh.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py --full --steps 2 --warmup 1 --extra-steps 2 --closed-loop-ticks 20 (all workloads)\n")
         fh.write("# units: KB per dispatch (mean over the dispatches of the pass; configs[2] mixes cold launches at the iteration cap with warm ones).  hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024\n")
         w = csv.writer(fh, quoting=csv.QUOTE_ALL)
         w.writerow(["kernel", "counter", "dispatches", "mean_KB"])
