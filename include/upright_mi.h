@@ -127,6 +127,14 @@ typedef struct upr_problem {
      * below ~1e-7 the stationarity residual of these problems is roundoff of the factorisation once the barrier
      * parameter is small).  <= 0: use qp_tol. */
     double qp_tol_stat;
+    /* end-effector box (end_effector_box_constraint.h:47-76, "end_effector_box_constraint"; controller.yaml:91-94): with
+     * ee_box != 0 the end-effector position p(q) stays inside p_d(t) + [ee_box_lower, ee_box_upper] at knots 1..N-1, p_d the
+     * interpolated target position of the end-effector cost.  Six state rows per knot, upper rows first:
+     * [p_d + ee_box_upper - p (3); p - (p_d + ee_box_lower) (3)], Jacobian [-J_p; J_p] in the q columns.  They are appended
+     * to the state-row block, whose slot order is [collision pairs n_pairs][projectile n_proj][box upper 3][box lower 3];
+     * softened by soft_poly like the other state-polytopic rows. */
+    int ee_box;
+    double ee_box_lower[3], ee_box_upper[3];
 } upr_problem;
 
 const char* upr_last_error(void);
@@ -255,8 +263,14 @@ int upr_batch_linearize_points(upr_batch* h, int n, const int* inst, const doubl
                                const double* u, double* g, double* gx, double* cost, double* grad,
                                double* hess, double* ee);
 /* ControllerInterface.getStateInputInequalityConstraintValue("obstacle_avoidance", t, x, u) (pybindings.cpp:417-419;
- * mpc_sim.py:191-219) at n states: d[n][n_pairs] and (may be NULL) dq[n][n_pairs][nq] = d d / d q */
+ * mpc_sim.py:191-219) at n states: d[n][n_pairs + n_proj] and (may be NULL) dq[n][n_pairs + n_proj][nq] = d d / d q.  The
+ * end-effector box rows are not among them (upr_batch_state_rows); fails when the problem has no pairs / projectile rows. */
 int upr_batch_obstacle_rows(upr_batch* h, int n, const double* x, double* d, double* dq);
+/* Every state row at n points (instance inst[n], time t[n], interface state x[n][nx_full]): d[n][no] and (may be NULL)
+ * dq[n][no][nq], no = n_pairs + n_proj + (ee_box ? 6 : 0), in the slot order of the record's row block
+ * [pairs][projectile][box upper 3][box lower 3].  The box rows depend on t and on the instance's targets
+ * (getStateInputInequalityConstraintValue("end_effector_box_constraint", t, x, u)). */
+int upr_batch_state_rows(upr_batch* h, int n, const int* inst, const double* t, const double* x, double* d, double* dq);
 /* constant d(object_dynamics)/du of instance `inst`: gu[ne][nu] */
 int upr_batch_eq_input_jacobian(upr_batch* h, int inst, double* gu);
 
@@ -268,7 +282,8 @@ int upr_batch_qp_step(upr_batch* h, double* dxs, double* dus);
  * (tests/kkt_check.py assembles the QP in numpy from upr_batch_get_lin and the problem constants): pi[B][N+1][nx]
  * costates of the dynamics (pi_0 unused), nu[B][N][ne] multipliers of the object-dynamics rows, yN[B][3 + 2 nq] of the
  * terminal equality, lam[B][N+1][ni] of the inequality rows with ni = 2 nx + 2 nu + np + no in the slot order
- * [x lower][x upper][u lower][u upper][friction rows][collision / projectile rows]; *ni_out = ni.  Pointers may be NULL. */
+ * [x lower][x upper][u lower][u upper][friction rows][state rows: collision pairs, projectile rows, end-effector box upper 3,
+ * lower 3]; *ni_out = ni.  Pointers may be NULL. */
 int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double* nu, double* yN, double* lam, int* ni_out);
 /* Slacks t[B][N+1][ni] of the inequality rows at the exit of the QP the last upr_batch_qp_kkt call solved (slot order of lam; 1 in
  * slots that are not rows of the knot).  lam / t are the barrier weights of the last interior-point iterate: with the costates they

@@ -47,6 +47,7 @@ class UprProblem(C.Structure):
         ("soft_L2_lower", d), ("soft_L2_upper", d), ("soft_L1_lower", d), ("soft_L1_upper", d),
         ("soft_eq", C.c_int),
         ("qp_tol_stat", d),
+        ("ee_box", C.c_int), ("ee_box_lower", d * 3), ("ee_box_upper", d * 3),
     ]
 
 
@@ -106,6 +107,9 @@ def problem_to_c(P):
     # the object-dynamics equality reaches HPIPM as a general constraint with lg = ug: `poly_ineq` softens it too
     o.soft_eq = int(bool(sl.get("equality", sl.get("poly_ineq"))))
     o.qp_tol_stat = float(getattr(P, "qp_tol_stat", 0.0) or 0.0)
+    o.ee_box = int(bool(P.ee_box))
+    if o.ee_box:
+        _fill(o.ee_box_lower, P.ee_box_lower); _fill(o.ee_box_upper, P.ee_box_upper)
     return o
 
 
@@ -137,6 +141,7 @@ PROTOTYPES = [
     ("upr_batch_linearize_points", C.c_int, [C.c_void_p, C.c_int, ip, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
     ("upr_batch_set_projectile_flag", C.c_int, [C.c_void_p, dp]),
     ("upr_batch_obstacle_rows", C.c_int, [C.c_void_p, C.c_int, dp, dp, dp]),
+    ("upr_batch_state_rows", C.c_int, [C.c_void_p, C.c_int, ip, dp, dp, dp, dp]),
     ("upr_batch_eq_input_jacobian", C.c_int, [C.c_void_p, C.c_int, dp]),
     ("upr_batch_qp_step", C.c_int, [C.c_void_p, dp, dp]),
     ("upr_batch_qp_kkt", C.c_int, [C.c_void_p, dp, dp, dp, dp, dp, dp, ip]),

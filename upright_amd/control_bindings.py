@@ -2,9 +2,9 @@
 
 Same class and attribute names; `ControllerInterface` drives one instance (B = 1) of the batched HIP
 engine through the C-ABI of libupright_mi.so.  Covered: the balancing OCP (object-dynamics equality, friction
-rows), obstacle avoidance over sphere pairs, up to four dynamic obstacles, the projectile-path constraint on the last, HPIPM
-slack settings, the linear feedback policy.  What the engine does not cover raises RuntimeError -- at
-construction for OCP terms (inertial alignment, end-effector box, operating points), at the call for the
+rows), obstacle avoidance over sphere pairs, up to four dynamic obstacles, the projectile-path constraint on the last, the
+end-effector box constraint, HPIPM slack settings, the linear feedback policy.  What the engine does not cover raises
+RuntimeError -- at construction for OCP terms (inertial alignment, operating points), at the call for the
 solver-internal getters (value function, Lagrangian, visualisation) -- the way the reference throws
 std::runtime_error; never a silent fallback.
 """
@@ -293,8 +293,6 @@ def problem_from_settings(s):
         raise RuntimeError("the MI355X engine supports %d dynamic obstacles" % MAX_DYNAMIC_OBSTACLES)
     if s.inertial_alignment_settings.cost_enabled or s.inertial_alignment_settings.constraint_enabled:
         raise RuntimeError("inertial alignment is outside the accelerated path (SURVEY.md section 2, row 12)")
-    if s.end_effector_box_constraint_enabled:
-        raise RuntimeError("end effector box constraint is outside the accelerated path (SURVEY.md section 2, row 13)")
     if s.use_operating_points:
         raise RuntimeError("operating points are not supported by the MI355X engine yet")
     if not s.balancing_settings.enabled:
@@ -366,6 +364,12 @@ def problem_from_settings(s):
             if d.o < 1:
                 raise RuntimeError("projectile_path_constraint needs a dynamic obstacle")
             robots.add_projectile_rows(P, s.projectile_path_collision_links, s.projectile_path_distances, s.projectile_path_scale)
+        if s.end_effector_box_constraint_enabled:
+            # controller_interface.cpp:257-270: six state rows around the interpolated target position (wrappers.py:239-250)
+            P.ee_box = True
+            P.ee_box_lower = np.asarray(s.xyz_lower, dtype=np.float64).reshape(-1).copy()
+            P.ee_box_upper = np.asarray(s.xyz_upper, dtype=np.float64).reshape(-1).copy()
+            P.validate()
     except ValueError as e:
         raise RuntimeError(str(e))
     return P.validate()
@@ -474,6 +478,11 @@ class ControllerInterface:
         return self._lin(t, x, u)["g"][0]
 
     def getStateInputInequalityConstraintValue(self, name, t, x, u):
+        if name == "end_effector_box_constraint" and self.problem.ee_box:
+            # end_effector_box_constraint.h:47-76: [p_d(t) + upper - p; p - (p_d(t) + lower)], the last six state rows
+            if self._mpc is None:
+                self._mpc = BatchMPC(self.problem, 1)
+            return self._mpc.state_rows(np.asarray(x, dtype=np.float64), t=float(t), jac=False)[0][-6:]
         if name in ("obstacle_avoidance", "projectile_constraint") and len(self.problem.pair_a) + len(self.problem.proj_sph) > 0:
             if self._mpc is None:
                 self._mpc = BatchMPC(self.problem, 1)

@@ -326,6 +326,9 @@ int check_problem(const upr_problem* P) {
     for (int i = 0; i < P->n_sph; ++i) if (P->sph_frame[i] > P->nq || (P->sph_frame[i] <= -2 && -2 - P->sph_frame[i] >= P->n_dyn)) return fail("sph_frame out of range");
     for (int i = 0; i < P->n_pairs; ++i)
         if (P->pair_a[i] < 0 || P->pair_a[i] >= P->n_sph || P->pair_b[i] < -1 || P->pair_b[i] >= P->n_sph || P->pair_a[i] == P->pair_b[i]) return fail("collision pair out of range");
+    if (P->ee_box) for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(P->ee_box_lower[i]) || !std::isfinite(P->ee_box_upper[i]) || P->ee_box_lower[i] > P->ee_box_upper[i])
+            return fail("end-effector box: lower and upper must be finite with lower <= upper");
     for (int i = 0; i < P->nc; ++i) {
         if (P->contact_body2[i] < 0 || P->contact_body2[i] >= P->nb) return fail("contact_body2 must index a balanced body");
         if (P->contact_body1[i] >= P->nb) return fail("contact_body1 out of range");
@@ -347,16 +350,17 @@ template <int NQ>
 int launch_linearize(upr_batch* h, const upr_lin_args& A) {
     static const int occ = getenv("UPR_LIN_OCC") ? atoi(getenv("UPR_LIN_OCC")) : 2;
     // knots per workgroup: several passes (their value walks side by side) for the plain instantiation without collision rows
-    const bool multi = UPR_LIN_ANALYTIC && !A.way_q && h->use_mfma && occ == 2 && A.d.no == 0;
+    // (the end-effector box rows come out of the position Jacobian in the last phase: they leave the layout as it is)
+    const bool multi = UPR_LIN_ANALYTIC && !A.way_q && h->use_mfma && occ == 2 && A.d.nsr == 0;
     // with collision rows (snapshot form, round 4: 156 instead of 480 doubles of LDS per knot for 16 spheres): UPR_LIN_ROW_PASSES
     // passes per workgroup (1, 2 or 3)
     static const int row_passes = getenv("UPR_LIN_ROW_PASSES") ? atoi(getenv("UPR_LIN_ROW_PASSES")) : UPR_LIN_ROW_PASSES_DEFAULT;
-    const bool multi_rows = UPR_LIN_ANALYTIC && UPR_LIN_OBS_SNAP && !A.way_q && h->use_mfma && occ == 2 && A.d.no > 0 && (row_passes == 2 || row_passes == 3);
+    const bool multi_rows = UPR_LIN_ANALYTIC && UPR_LIN_OBS_SNAP && !A.way_q && h->use_mfma && occ == 2 && A.d.nsr > 0 && (row_passes == 2 || row_passes == 3);
     // no collision rows, no orientation cost: the one-round kernel of upr_linearize2.h, as many knots per workgroup as three
     // workgroups per CU hold in LDS and one tangent pass takes in one trip (28 for the headline shape: 768 workgroups)
     if (h->lin2 && upr_lin2_eligible(A) && h->use_mfma && occ == 2) {
         const upr_lin2_lay lay = upr_lin2_layout(A.d, h->P.n_sph);
-        const int npre = ((UPR_LIN2_NPRE + 1) & ~1) + (A.d.no > 0 ? upr_lin2_table_doubles(h->P.n_sph) : 0);
+        const int npre = ((UPR_LIN2_NPRE + 1) & ~1) + (A.d.nsr > 0 ? upr_lin2_table_doubles(h->P.n_sph) : 0);
         int kpw = (int)((UPR_LIN2_LDS_BUDGET - npre * sizeof(double)) / (lay.per * sizeof(double)));
         if (kpw > 256 / NQ) kpw = 256 / NQ;
         if (kpw > 64) kpw = 64;
@@ -739,7 +743,8 @@ int launch_linesearch(upr_batch* h, const upr_ls_args& A0) {
     // exactly the headline's contact structure (one body on the tray, four frictional contacts): every bound a constant
     const bool st = A.stage_full != 0;   // (compile-time in the kernel: its staged arrays are LDS pointers, not generic ones)
     if (h->d.nfc == 12 && h->d.nb == 1 && h->P.nf == 3 && h->P.nc == 4 && h->d.no == 0) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, true, false, true> : upr_linesearch_kernel<NQ, 128, 12, 1, true, false, false>);
-    // ... the same with collision / projectile rows (configs[4], the obstacle experiments: round 5)
+    // ... the same with state rows: collision / projectile rows (configs[4], the obstacle experiments: round 5), the end-effector box
+    // (a box-only problem skips the sphere walk: upr_ls_knot)
     else if (h->d.nfc == 12 && h->d.nb == 1 && h->P.nf == 3 && h->P.nc == 4) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, true, true, true> : upr_linesearch_kernel<NQ, 128, 12, 1, true, true, false>);
     else if (h->d.nfc <= 12 && h->d.nb == 1) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, false, true, true> : upr_linesearch_kernel<NQ, 128, 12, 1, false, true, false>);
     else launch(st ? upr_linesearch_kernel<NQ, 128, 3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true, true> : upr_linesearch_kernel<NQ, 128, 3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true, false>);
@@ -933,7 +938,7 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
     if (d.nx > UPR_LPK) { fail("nx exceeds the 32 tangent lanes of the linearisation kernel"); delete h; return nullptr; }
     // collision rows (state-polytopic inequalities) are implemented in the generic kernel only
     const bool soft = P->soft_state_box || P->soft_input_box || P->soft_poly || P->soft_eq;
-    const bool plain = P->n_pairs + P->n_proj == 0 && !soft;   // rows only the generic kernel has
+    const bool plain = h->d.no == 0 && !soft;   // rows the second-structure kernel does not have
     h->use_qp3 = qp3_variant(*P, h->d);
     h->use_qp2 = qp2_has_shape(*P) && plain;
     const bool forced_other = (getenv("UPR_QP_KERNEL") && atoi(getenv("UPR_QP_KERNEL")) < 3) || (getenv("UPR_QP_GENERIC") && atoi(getenv("UPR_QP_GENERIC")) != 0);
@@ -1243,24 +1248,40 @@ int upr_batch_linearize_points(upr_batch* h, int n, const int* inst, const doubl
     return 0;
 }
 
-int upr_batch_obstacle_rows(upr_batch* h, int n, const double* x, double* dd, double* dq) {
-    UPR_ENTER(h);
+// the first `nr` state rows (slot order of the record) at n points (inst[n], t[n], interface states x[n][nx_full]): d[n][nr], dq[n][nr][nq]
+static int state_rows_impl(upr_batch* h, int n, const int* inst, const double* t, const double* x, int nr, double* dd, double* dq) {
     const upr_dims& d = h->d;
-    if (d.no == 0) return fail("upr_batch_obstacle_rows: the problem has no collision pairs / projectile rows");
-    if (n <= 0) return 0;
-    std::vector<int> inst(n, 0);
-    std::vector<double> t(n, 0.0), u((size_t)n * d.nu, 0.0), rec, xr((size_t)n * d.nx), dyn((size_t)n * 9 * h->P.n_dyn);
+    std::vector<double> u((size_t)n * d.nu, 0.0), rec, xr((size_t)n * d.nx), dyn((size_t)n * 9 * h->P.n_dyn);
     for (int i = 0; i < n; ++i) {   // interface states: [robot x, obstacle r v a]
         std::memcpy(xr.data() + (size_t)i * d.nx, x + (size_t)i * h->nxf, sizeof(double) * d.nx);
         if (h->P.n_dyn) std::memcpy(dyn.data() + (size_t)i * 9 * h->P.n_dyn, x + (size_t)i * h->nxf + d.nx, sizeof(double) * 9 * h->P.n_dyn);
     }
-    if (linearize_points_impl(h, n, inst.data(), t.data(), xr.data(), u.data(), rec, nullptr, h->P.n_dyn ? dyn.data() : nullptr)) return 1;
+    if (linearize_points_impl(h, n, inst, t, xr.data(), u.data(), rec, nullptr, h->P.n_dyn ? dyn.data() : nullptr)) return 1;
     for (int i = 0; i < n; ++i) {
         const double* r = rec.data() + (size_t)i * d.lin_stride + d.lin_obs;
-        std::memcpy(dd + (size_t)i * d.no, r, sizeof(double) * d.no);
-        if (dq) std::memcpy(dq + (size_t)i * d.no * d.nq, r + d.no, sizeof(double) * d.no * d.nq);
+        std::memcpy(dd + (size_t)i * nr, r, sizeof(double) * nr);
+        if (dq) std::memcpy(dq + (size_t)i * nr * d.nq, r + d.no, sizeof(double) * nr * d.nq);   // (row r's gradient: r + no + r nq)
     }
     return 0;
+}
+
+int upr_batch_obstacle_rows(upr_batch* h, int n, const double* x, double* dd, double* dq) {
+    UPR_ENTER(h);
+    const upr_dims& d = h->d;
+    if (d.nsr == 0) return fail("upr_batch_obstacle_rows: the problem has no collision pairs / projectile rows");
+    if (n <= 0) return 0;
+    std::vector<int> inst(n, 0);
+    std::vector<double> t(n, 0.0);
+    return state_rows_impl(h, n, inst.data(), t.data(), x, d.nsr, dd, dq);
+}
+
+int upr_batch_state_rows(upr_batch* h, int n, const int* inst, const double* t, const double* x, double* dd, double* dq) {
+    UPR_ENTER(h);
+    const upr_dims& d = h->d;
+    if (d.no == 0) return fail("upr_batch_state_rows: the problem has no state rows");
+    if (n <= 0) return 0;
+    for (int i = 0; i < n; ++i) if (inst[i] < 0 || inst[i] >= h->B) return fail("instance index out of range");
+    return state_rows_impl(h, n, inst, t, x, d.no, dd, dq);
 }
 
 int upr_batch_eq_input_jacobian(upr_batch* h, int inst, double* gu) {

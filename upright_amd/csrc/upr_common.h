@@ -96,7 +96,8 @@ static inline UPR_HD double upr_rcp(double x) {
 
 // derived dimensions
 struct upr_dims {
-    int nq, nb, nc, nf, N, nx, nu, nfc, ne, np, neN, no;   // no: collision pairs (state rows at knots 1..N-1)
+    int nq, nb, nc, nf, N, nx, nu, nfc, ne, np, neN, no;   // no: state rows at knots 1..N-1 (nsr + nbox)
+    int nsr, nbox;   // of them: rows from the collision spheres (pairs, then projectile rows), then the end-effector box (0 or 6)
     // per-knot linearisation record (doubles): [g ne][gx ne*nx][cost 1][grad nq][hess nq(nq+1)/2]
     int lin_g, lin_gx, lin_cost, lin_grad, lin_hess, lin_obs, lin_stride;   // lin_obs: [d no][dd/dq no*nq]
     // inequality layout per stage: [x lo nx][x hi nx] (k >= 1) [u lo nu][u hi nu][poly np] (k < N)
@@ -119,7 +120,7 @@ static inline UPR_HD upr_dims upr_make_dims(const upr_problem* P) {
     d.eq_scale = 1.0 / sqrt(6.0 * P->nb);
     d.neN = P->terminal_constraint ? 3 + 2 * P->nq : 0;
     d.lin_g = 0; d.lin_gx = d.ne; d.lin_cost = d.lin_gx + d.ne * d.nx; d.lin_grad = d.lin_cost + 1;
-    d.no = P->n_pairs + P->n_proj; d.n_dyn = P->n_dyn;
+    d.nsr = P->n_pairs + P->n_proj; d.nbox = P->ee_box ? 6 : 0; d.no = d.nsr + d.nbox; d.n_dyn = P->n_dyn;
     d.lin_hess = d.lin_grad + d.nq; d.lin_obs = d.lin_hess + d.nq * (d.nq + 1) / 2; d.lin_stride = d.lin_obs + d.no * (1 + d.nq);
     d.ni_stage = 2 * d.nx + 2 * d.nu + d.np + d.no;
     d.ss_kx = 0; d.ss_hjj = d.ss_kx + d.nq * d.nx; d.ss_hff = d.ss_hjj + d.nq * d.nq;
@@ -160,6 +161,12 @@ static inline UPR_HD void upr_target_position(const upr_problem* P, const double
         alpha = (P->way_t[idx + 1] - t) / (P->way_t[idx + 1] - P->way_t[idx]);
     }
     for (int i = 0; i < 3; ++i) pd[i] = alpha * way_p[3 * idx + i] + (1.0 - alpha) * way_p[3 * (idx + 1) + i];
+}
+
+// end-effector box row i = 0..5 (end_effector_box_constraint.h:47-76) from the position error e = p - p_d: the upper rows
+// p_d + upper - p first, then p - (p_d + lower); d row / d q = -J_p (upper), +J_p (lower)
+static inline UPR_HD double upr_box_row(const upr_problem* P, int i, const double* e) {
+    return (i < 3) ? P->ee_box_upper[i] - e[i] : e[i - 3] - P->ee_box_lower[i - 3];
 }
 
 // reference_trajectory.h:18-47 (orientation part): the target orientation is the SLERP of the waypoint quaternions

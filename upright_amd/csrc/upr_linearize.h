@@ -41,9 +41,9 @@ static UPR_HDI int upr_lin_lds_snap(const upr_dims& d, int n_sph = 0) {
 #if UPR_LIN_OBS_SNAP && UPR_LIN_ANALYTIC
     // (the obstacle area only where there are obstacles: 37 doubles per knot put configs[2]'s sixteen knots beyond 80 KB, i.e. one
     //  workgroup per CU instead of two: 0.39 -> 0.57 ms)
-    return d.no > 0 ? upr_lin_lds_dyn(d, n_sph) + (d.n_dyn > 0 ? ((9 * d.n_dyn + 1 + 1) & ~1) : 0) : upr_lin_lds_base(d);
+    return d.nsr > 0 ? upr_lin_lds_dyn(d, n_sph) + (d.n_dyn > 0 ? ((9 * d.n_dyn + 1 + 1) & ~1) : 0) : upr_lin_lds_base(d);
 #else
-    return upr_lin_lds_base(d) + (d.no > 0 ? n_sph * 3 * (1 + d.nq) : 0);
+    return upr_lin_lds_base(d) + (d.nsr > 0 ? n_sph * 3 * (1 + d.nq) : 0);
 #endif
 }
 static UPR_HDI int upr_lin_lds_doubles(const upr_dims& d, int n_sph = 0) { return (upr_lin_lds_snap(d, n_sph) + d.nq * UPR_SNAP_J + UPR_SNAP_E + 1) & ~1; }
@@ -237,7 +237,7 @@ static UPR_HDI void upr_lin_phase1a(const upr_lin_args& A, const upr_lin_point& 
 #if UPR_LIN_ANALYTIC
     // (x: the state straight from the input when the staging into LDS runs at the same time on other waves)
     if (lane == 0) upr_ee_walk_snap<NQ>(A.P, x ? x : sh, sh + upr_lin_lds_sc(A.d), sh + upr_lin_lds_snap(A.d, A.P->n_sph),
-                                        (UPR_LIN_OBS_SNAP && A.d.no > 0) ? sh + upr_lin_lds_frames(A.d, A.P->n_sph) : nullptr);
+                                        (UPR_LIN_OBS_SNAP && A.d.nsr > 0) ? sh + upr_lin_lds_frames(A.d, A.P->n_sph) : nullptr);
 #endif
 }
 
@@ -384,7 +384,7 @@ static UPR_HDI void upr_lin_obs_row(const upr_lin_args& A, const upr_lin_point& 
 }
 template <int NQ>
 static UPR_HDI void upr_lin_phase_obs_b(const upr_lin_args& A, const upr_lin_point& q, int lane, const double* sh) {
-    for (int r = lane; r < A.d.no; r += UPR_LPK) upr_lin_obs_row<NQ>(A, q, r, sh);
+    for (int r = lane; r < A.d.nsr; r += UPR_LPK) upr_lin_obs_row<NQ>(A, q, r, sh);
 }
 #else
 template <int NQ>
@@ -412,7 +412,7 @@ static UPR_HDI void upr_lin_phase_obs_b(const upr_lin_args& A, const upr_lin_poi
     double ro[3], vo[3], ao[3];
     upr_lin_obstacle(A, q, A.P->n_dyn > 0 ? A.P->n_dyn - 1 : 0, ro, vo, ao);   // (the projectile rows follow the last obstacle: state.tail(9))
     const double flag = A.pflag ? A.pflag[q.b] : 0.0;
-    for (int r = lane; r < d.no; r += UPR_LPK) {
+    for (int r = lane; r < d.nsr; r += UPR_LPK) {
         int sa, sb; double n[3], w;
         q.out[d.lin_obs + r] = upr_state_row(P, r, [&](int s, int i) { return sc[(s * 3 + i) * (1 + NQ)]; }, ro, vo, ao, flag, &sa, &sb, n, &w);
         for (int j = 0; j < NQ; ++j) {
@@ -424,7 +424,20 @@ static UPR_HDI void upr_lin_phase_obs_b(const upr_lin_args& A, const upr_lin_poi
 }
 #endif
 
-// phase 2 (VALU path): gradient, Gauss-Newton Hessian, cost from the LDS-staged position Jacobian
+// end-effector box row i = 0..5 of one knot (slot nsr + i of the state rows, knots 1..N-1 as the collision rows): value out of
+// the position error e = p - p_d, gradient -J_p (upper rows) or +J_p (lower rows); J: J_p [3][NQ] (both read from the knot's LDS
+// area once the position error is in place; P: a record that holds the box)
+template <int NQ>
+static UPR_HDI void upr_lin_job_box(const upr_dims& d, const upr_problem* P, const upr_lin_point& q, int i, const double* e, const double* J) {
+    if (q.terminal) return;
+    const int r = d.nsr + i, a = (i < 3) ? i : i - 3;
+    const double s = (i < 3) ? -1.0 : 1.0;
+    q.out[d.lin_obs + r] = upr_box_row(P, i, e);
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) q.out[d.lin_obs + d.no + r * NQ + j] = s * J[a * NQ + j];
+}
+
+// phase 2 (VALU path): gradient, Gauss-Newton Hessian, cost from the LDS-staged position Jacobian (+ the end-effector box rows)
 template <int NQ, bool ORI = false>
 static UPR_HDI void upr_lin_phase2(const upr_lin_args& A, const upr_lin_point& q, int lane, const double* sh) {
     const upr_dims& d = A.d;
@@ -433,6 +446,7 @@ static UPR_HDI void upr_lin_phase2(const upr_lin_args& A, const upr_lin_point& q
     const double* se = sJ + 6 * d.nq;
     constexpr int nr = ORI ? 6 : 3;   // error rows: position (+ orientation)
     if (!q.terminal) {
+        if (d.nbox > 0 && lane < 6) upr_lin_job_box<NQ>(d, A.P, q, lane, se, sJ);
         if (lane < NQ) {
             double g = 0.0;
             for (int r = 0; r < nr; ++r) g += W[r] * se[r] * sJ[r * NQ + lane];
@@ -497,7 +511,7 @@ __global__ void __launch_bounds__(256, OCC) upr_linearize_kernel(upr_lin_args A)
     }
 #endif
 #if UPR_LIN_OBS_SNAP && UPR_LIN_ANALYTIC
-    if (A.d.no > 0 && A.dyn) {   // the obstacles' states at every knot of the workgroup (read by the rows behind three barriers)
+    if (A.d.nsr > 0 && A.dyn) {   // the obstacles' states at every knot of the workgroup (read by the rows behind three barriers)
         const int nd = A.P->n_dyn;   // (A.P is still the global record here)
         for (int idx = threadIdx.x; idx < 8 * NP * nd; idx += 256) {
             const int sp = idx / nd, oi = idx - sp * nd;
@@ -546,12 +560,12 @@ __global__ void __launch_bounds__(256, OCC) upr_linearize_kernel(upr_lin_args A)
         if (p < A.npoints) { const upr_lin_point q = upr_lin_locate(A, p); upr_lin_phase1<NQ, ORI>(A, q, lane, smem + slot * per); }
     }
     UPR_LIN_STAMP(2);
-    if (A.d.no > 0) {
+    if (A.d.nsr > 0) {
 #if UPR_LIN_OBS_SNAP && UPR_LIN_ANALYTIC
         // (snapshot form: the 32 lanes of a knot group sit in one wave, so a wave-local ordering point separates placing the
         // spheres from the rows that read them; the group's lanes take (pass, sphere) and (pass, row) jobs of ALL its passes at
         // once -- a problem with five rows per knot keeps ten lanes busy for one trip instead of five lanes for two)
-        const int ns = A.P->n_sph, no = A.d.no;
+        const int ns = A.P->n_sph, no = A.d.nsr;
 #pragma unroll 1
         for (int idx = lane; idx < NP * ns; idx += UPR_LPK) {
             const int pp = idx / ns, s = idx - pp * ns, slot = pp * 8 + sub, p = base + slot;
@@ -631,6 +645,7 @@ __global__ void __launch_bounds__(256, OCC) upr_linearize_kernel(upr_lin_args A)
             const double* se = sJ + 6 * A.d.nq;
             constexpr int nr = ORI ? 6 : 3;
             if (!q.terminal) {
+                if (A.d.nbox > 0 && lane < 6) upr_lin_job_box<NQ>(A.d, A.P, q, lane, se, sJ);
                 if (lane < NQ) {
                     double g = 0.0;
                     for (int r = 0; r < nr; ++r) g += W[r] * se[r] * sJ[r * NQ + lane];

@@ -31,7 +31,7 @@ static UPR_HDI upr_lin2_lay upr_lin2_layout(const upr_dims& d, int n_sph) {
     upr_lin2_lay l;
     l.gf = 0; l.e = d.ne; l.js = (l.e + 3 + 1) & ~1; l.snap = l.js + ((3 * d.nq + 1) & ~1);
     l.obs = l.snap + upr_snap_at(d.nq, true) + UPR_SNAP_E;   // (joint 0's snapshot compact: upr_kin.h, COMPACT0)
-    l.per = (l.obs + (d.no > 0 ? 3 * n_sph : 0)) | 1;   // (odd: the walk lanes -- one per knot, the same offset in every knot's area -- then hit different LDS banks)
+    l.per = (l.obs + (d.nsr > 0 ? 3 * n_sph : 0)) | 1;   // (odd: the walk lanes -- one per knot, the same offset in every knot's area -- then hit different LDS banks)
     return l;
 }
 static UPR_HDI bool upr_lin2_eligible(const upr_lin_args& A) { return A.way_q == nullptr && A.Df != nullptr; }
@@ -343,13 +343,13 @@ static UPR_HDI void upr_lin2_knot(const upr_lin_args& A, const upr_lin_point& q,
     const upr_lin2_lay lay = upr_lin2_layout(d, A.P->n_sph);
     const upr_problem* P = A.P;
     for (int j = 0; j < NQ; ++j) upr_sincos(q.x[j], sh + lay.js + 2 * j, sh + lay.js + 2 * j + 1);
-    if (d.no > 0) {
+    if (d.nsr > 0) {
         double tab[UPR_LIN2_SPH_DOUBLES];
         for (int i = 0; i < UPR_MAX_SPHERES || i < NQ + 2; ++i) upr_lin2_sphere_table(P, NQ, i, tab);
         upr_lin2_place place{tab, sh + lay.obs};
         upr_ee_walk_snap<NQ, upr_lin2_place, true>(P, q.x, sh + lay.js, sh + lay.snap, nullptr, place);
         for (int s2 = 0; s2 < P->n_sph; ++s2) upr_lin2_job_fixed_sphere(A, P, q, s2, sh + lay.obs);
-        for (int r = 0; r < d.no; ++r) upr_lin2_job_row<NQ>(A, P, P, q, r, sh + lay.snap, sh + lay.obs);
+        for (int r = 0; r < d.nsr; ++r) upr_lin2_job_row<NQ>(A, P, P, q, r, sh + lay.snap, sh + lay.obs);
     } else upr_ee_walk_snap<NQ, upr_no_hook, true>(P, q.x, sh + lay.js, sh + lay.snap, nullptr);
     for (int r = 0; r < d.ne; ++r) upr_lin2_job_dff(A, q, r, sh, lay);
     upr_target_position(P, A.way_p + (size_t)q.b * P->n_way * 3, q.t, sh + lay.e);
@@ -360,6 +360,7 @@ static UPR_HDI void upr_lin2_knot(const upr_lin_args& A, const upr_lin_point& q,
     const double* T = sh + lay.snap + upr_snap_at(NQ, true);
     for (int r = 0; r < 3; ++r) { sh[lay.e + r] = T[9 + r] - sh[lay.e + r]; if (A.ee_out) A.ee_out[(size_t)q.p * 3 + r] = T[9 + r]; }
     for (int j = 0; j < NQ; ++j) { upr_lin2_job_grad<NQ>(A, P, q, j, sh, lay); upr_lin2_job_hess_row<NQ>(A, P, q, j, sh, lay); }
+    for (int i = 0; i < d.nbox; ++i) upr_lin_job_box<NQ>(d, P, q, i, sh + lay.e, sh + lay.js);
 }
 
 #ifndef UPR_HOST_EMU
@@ -372,7 +373,8 @@ static UPR_HDI void upr_lin2_knot(const upr_lin_args& A, const upr_lin_point& q,
 // barrier 1: prefix of the record, sin / cos (a lane per (knot, joint));  wave 0: the value walks, a lane per knot, beside
 // waves 1 - 3: Df f (a lane per (knot, row)) and the target positions;  barrier 2;  three tangent passes, a class each, a lane
 // per (knot, joint), then the residuals' values and the position errors;  barrier 3;  Hessians on the matrix cores (a knot per
-// wave and trip), gradients and costs.
+// wave and trip), gradients and costs, and (end-effector box) its six rows, a lane per (knot, row), out of the position error
+// and J_p already in LDS.
 template <int NQ>
 __global__ void __launch_bounds__(256, 3) upr_linearize2_kernel(upr_lin_args A, int kpw, int n_sph) {
     extern __shared__ __attribute__((aligned(16))) double smem_all[];
@@ -381,7 +383,7 @@ __global__ void __launch_bounds__(256, 3) upr_linearize2_kernel(upr_lin_args A, 
     const upr_dims& d = A.d;
     const upr_lin2_lay lay = upr_lin2_layout(d, n_sph);
     double* tab = smem_all + ((NPRE + 1) & ~1);   // (the sphere table: problems with collision rows only)
-    double* smem = tab + (d.no > 0 ? upr_lin2_table_doubles(n_sph) : 0);
+    double* smem = tab + (d.nsr > 0 ? upr_lin2_table_doubles(n_sph) : 0);
     const int tid = threadIdx.x, base = blockIdx.x * kpw;
     const int nk = (A.npoints - base < kpw) ? A.npoints - base : kpw;
 #ifdef UPR_LIN_PROF
@@ -393,7 +395,7 @@ __global__ void __launch_bounds__(256, 3) upr_linearize2_kernel(upr_lin_args A, 
         for (int i = tid; i < NPRE; i += 256) smem_all[i] = src[i];
     }
     static_assert(UPR_MAX_SPHERES >= UPR_MAX_JOINTS + 2, "one lane per entry of the sphere table");
-    if (d.no > 0 && tid < UPR_MAX_SPHERES) upr_lin2_sphere_table(PG, NQ, tid, tab);
+    if (d.nsr > 0 && tid < UPR_MAX_SPHERES) upr_lin2_sphere_table(PG, NQ, tid, tab);
     for (int job = tid; job < nk * NQ; job += 256) {
         const int s = job / NQ, j = job - s * NQ;
         const upr_lin_point q = upr_lin_locate(A, base + s);
@@ -408,11 +410,11 @@ __global__ void __launch_bounds__(256, 3) upr_linearize2_kernel(upr_lin_args A, 
         if (tid < nk) {
             const upr_lin_point q = upr_lin_locate(A, base + tid);
             double* sh = smem + tid * lay.per;
-            if (d.no > 0) { upr_lin2_place place{tab, sh + lay.obs}; upr_ee_walk_snap<NQ, upr_lin2_place, true>(P, q.x, sh + lay.js, sh + lay.snap, nullptr, place); }
+            if (d.nsr > 0) { upr_lin2_place place{tab, sh + lay.obs}; upr_ee_walk_snap<NQ, upr_lin2_place, true>(P, q.x, sh + lay.js, sh + lay.snap, nullptr, place); }
             else upr_ee_walk_snap<NQ, upr_no_hook, true>(P, q.x, sh + lay.js, sh + lay.snap, nullptr);
         }
     } else {
-        if (d.no > 0) for (int idx = tid - 64; idx < nk * n_sph; idx += 192) {   // the spheres that do not ride on the chain
+        if (d.nsr > 0) for (int idx = tid - 64; idx < nk * n_sph; idx += 192) {   // the spheres that do not ride on the chain
             const int s = idx / n_sph, sp = idx - s * n_sph;
             const upr_lin_point q = upr_lin_locate(A, base + s);
             upr_lin2_job_fixed_sphere(A, PG, q, sp, smem + s * lay.per + lay.obs);
@@ -450,8 +452,8 @@ __global__ void __launch_bounds__(256, 3) upr_linearize2_kernel(upr_lin_args A, 
         const upr_lin_point q = upr_lin_locate(A, base + s);
         upr_lin2_job_value(A, P, q, b, NQ, smem + s * lay.per, lay);
     }
-    if (d.no > 0) for (int job = tid; job < nk * d.no; job += 256) {   // collision / projectile rows
-        const int s = job / d.no, r = job - s * d.no;
+    if (d.nsr > 0) for (int job = tid; job < nk * d.nsr; job += 256) {   // collision / projectile rows
+        const int s = job / d.nsr, r = job - s * d.nsr;
         const upr_lin_point q = upr_lin_locate(A, base + s);
         upr_lin2_job_row<NQ>(A, PG, P, q, r, smem + s * lay.per + lay.snap, smem + s * lay.per + lay.obs);
     }
@@ -488,6 +490,11 @@ __global__ void __launch_bounds__(256, 3) upr_linearize2_kernel(upr_lin_args A, 
         const int s = job / NQ, j = job - s * NQ;
         const upr_lin_point q = upr_lin_locate(A, base + s);
         upr_lin2_job_grad<NQ>(A, PG, q, j, smem + s * lay.per, lay);
+    }
+    if (d.nbox > 0) for (int job = tid; job < nk * 6; job += 256) {   // end-effector box rows: a lane per (knot, row)
+        const int s = job / 6, i = job - s * 6;
+        const upr_lin_point q = upr_lin_locate(A, base + s);
+        upr_lin_job_box<NQ>(d, PG, q, i, smem + s * lay.per + lay.e, smem + s * lay.per + lay.js);
     }
     UPR_LIN2_STAMP(4);
 }

@@ -62,7 +62,7 @@ static UPR_HDI void upr_object_wrench_single(const upr_problem* P, const double*
 // Performance terms [cost, dyn_sse, eq_sse, ineq_sse] of a trajectory (Xs [N+1][nx], Us [N][nu]), in two parts.
 //
 // (1) upr_ls_knot: what needs the end effector's state at the knot -- end-effector cost, object-dynamics equality, collision /
-//     projectile rows, terminal position error -- a lane per knot walking the chain on plain values.
+//     projectile rows, end-effector box rows, terminal position error -- a lane per knot walking the chain on plain values.
 // (2) upr_ls_flat_terms: everything else -- quadratic state-input cost, boxes, friction rows, dynamics defects, terminal
 //     velocity / acceleration -- element by element over the flat lanes (a lane per knot summing its 27 + 21 elements one
 //     after another was half of the kernel's run time: one wave, 21 of its lanes, ~500 LDS reads each).
@@ -70,7 +70,8 @@ static UPR_HDI void upr_object_wrench_single(const upr_problem* P, const double*
 //     instead of walking again, and the step norms and the Armijo descent metric (cost gradient . step) are summed in the same pass.
 //
 // NFM / NBM: compile-time bounds of nf nc / nb.  EXACT: the problem has exactly nf = 3, nc = NFM / 3 contacts, nb = NBM bodies
-// (checked by the launcher; OBS: with collision / projectile rows): every loop bound of the knot's part is then a constant and its
+// (checked by the launcher; OBS: with state rows -- collision / projectile rows by a sphere walk where there are any, end-effector box
+// rows out of the end effector's position): every loop bound of the knot's part is then a constant and its
 // input vector and wrenches stay in registers (with run-time bounds they were indexed dynamically: 1.2 KB of scratch per lane).
 // Xt / Ut: the trial trajectory of the instance (staged by the workgroup, LDS on the device); sc: (sin, cos) of the trial joint
 // angles of every knot, [N + 1][NQ][2]; pd: the knot's target position (it does not depend on the step length)
@@ -99,17 +100,24 @@ static UPR_HDI void upr_ls_knot(const upr_ls_args& A, int b, int k, const double
         if (EXACT && NBM == 1) upr_object_wrench_single<NFM / 3>(P, bpv, F, Fw);
         else upr_object_wrenches(P, bp, F, Fw);
     }
-    if (OBS && d.no > 0 && k >= 1 && k < N) {   // collision rows (knots 1..N-1); !OBS: the problem has none
-        double dd[UPR_MAX_PAIRS + 8], xo[9 * UPR_MAX_DYN];
+    if (OBS && d.nsr > 0 && k >= 1 && k < N) {   // collision / projectile rows (knots 1..N-1); !OBS: the problem has none
+        double dd[UPR_MAX_PAIRS + 8], xo[9 * UPR_MAX_DYN];   // (n_pairs + n_proj entries; the box rows follow from E.p below)
         if (A.dyn) for (int oi = 0; oi < P->n_dyn; ++oi) upr_obstacle_at(A.dyn + ((size_t)b * P->n_dyn + oi) * 9, k * h, xo + 9 * oi, xo + 9 * oi + 3, xo + 9 * oi + 6);
         upr_obstacle_values<NQ>(P, X, A.dyn ? xo : nullptr, A.pflag ? A.pflag[b] : 0.0, dd);
-        for (int r = 0; r < d.no; ++r) { const double v = fmin(0.0, dd[r]); iq += h * v * v; }
+        for (int r = 0; r < d.nsr; ++r) { const double v = fmin(0.0, dd[r]); iq += h * v * v; }
     }
     upr_ee<double> E;
     upr_ee_kinematics<double, NQ, true>(P, X, -1, E, sc + k * 2 * NQ);
     if (k < N) {
-        double c = 0.0;
-        for (int r = 0; r < 3; ++r) { double e = E.p[r] - pd[r]; c += 0.5 * P->Wee[r] * e * e; }
+        // (+ the end-effector box rows, knots 1..N-1, out of the same position error: no walk, and nothing kept live beyond this loop;
+        // OBS instantiations only -- the launcher hands a box to those -- so that the row-free ones keep their registers)
+        double c = 0.0, bx = 0.0;
+        for (int r = 0; r < 3; ++r) {
+            const double e = E.p[r] - pd[r];
+            c += 0.5 * P->Wee[r] * e * e;
+            if (OBS && d.nbox > 0) { const double vu = fmin(0.0, P->ee_box_upper[r] - e), vl = fmin(0.0, e - P->ee_box_lower[r]); bx += vu * vu + vl * vl; }
+        }
+        if (OBS && k >= 1) iq += h * bx;
         if (A.way_q) {
             double Rr[9], eo[3];
             upr_target_rotation(P, A.way_q + (size_t)b * P->n_way * 4, A.t0[b] + k * h, Rr);

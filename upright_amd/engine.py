@@ -172,6 +172,17 @@ class BatchMPC:
         check(self._lib.upr_batch_obstacle_rows(self._h, n, ptr(x), ptr(d), ptr(dq) if jac else None))
         return (d, dq) if jac else d
 
+    def state_rows(self, x, t=None, inst=None, jac=True):
+        """Every state row at n points: d (n, no) and d d / d q (n, no, nq), no = n_pairs + n_proj (+ 6 with the end-effector box),
+        slot order [pairs][projectile][box upper 3][box lower 3].  The box rows depend on the time and on the instance's targets."""
+        x = cont(x).reshape(-1, self.nxf)
+        n, no, nq = x.shape[0], self.problem.n_state_rows, self.problem.nq
+        t = cont(np.zeros(n) if t is None else np.broadcast_to(np.asarray(t, dtype=np.float64), (n,)))
+        inst = cont(np.zeros(n) if inst is None else np.broadcast_to(np.asarray(inst), (n,)), dtype=np.int32)
+        d = np.zeros((n, no)); dq = np.zeros((n, no, nq))
+        check(self._lib.upr_batch_state_rows(self._h, n, iptr(inst), ptr(t), ptr(x), ptr(d), ptr(dq) if jac else None))
+        return (d, dq) if jac else d
+
     def set_projectile_flag(self, s):
         """Activation flag of the projectile rows per instance (8th entry of the target state)."""
         s = cont(np.broadcast_to(np.asarray(s, dtype=np.float64), (self.B,)))
@@ -192,7 +203,7 @@ class BatchMPC:
         """One QP at the current trajectory: step and the multipliers the kernel ended with (see upr_batch_qp_kkt)."""
         P = self.problem
         ni = C.c_int(0)
-        nin = 2 * self.nx + 2 * self.nu + (5 * P.nc if P.nf == 3 else 0) + len(P.pair_a) + len(P.proj_sph)
+        nin = 2 * self.nx + 2 * self.nu + (5 * P.nc if P.nf == 3 else 0) + P.n_state_rows
         out = dict(dx=np.zeros((self.B, self.N + 1, self.nx)), du=np.zeros((self.B, self.N, self.nu)),
                    pi=np.zeros((self.B, self.N + 1, self.nx)), nu=np.zeros((self.B, self.N, self.ne)),
                    yN=np.zeros((self.B, 3 + 2 * P.nq if P.terminal_constraint else 0)), lam=np.zeros((self.B, self.N + 1, nin)))

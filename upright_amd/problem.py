@@ -67,6 +67,11 @@ class Problem:
     # HPIPM soft constraints (hpipm_interface SlackSettings, wrappers.py:121-143): None / {} = hard constraints; keys
     # state_box, input_box, poly_ineq (bool), lower/upper_L2_penalty (100), lower/upper_L1_penalty (0)
     slacks: dict = None
+    # end-effector box (end_effector_box_constraint.h:47-76; controller.yaml:91-94): p(q) inside p_d(t) + [lower, upper] at knots
+    # 1..N-1, six state rows after the collision / projectile rows
+    ee_box: bool = False
+    ee_box_lower: np.ndarray = field(default_factory=lambda: np.full(3, -1.0))
+    ee_box_upper: np.ndarray = field(default_factory=lambda: np.full(3, 1.0))
 
     @property
     def nq(self):
@@ -105,7 +110,18 @@ class Problem:
             raise ValueError("Wee must hold six non-negative weights")
         if self.body_params.shape != (self.nb, 10):
             raise ValueError("body_params must be (nb, 10)")
+        if self.ee_box:
+            lo, hi = np.asarray(self.ee_box_lower, dtype=np.float64), np.asarray(self.ee_box_upper, dtype=np.float64)
+            if lo.shape != (3,) or hi.shape != (3,):
+                raise ValueError("ee_box_lower and ee_box_upper must hold three values each")
+            if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))) or np.any(lo > hi):
+                raise ValueError("end-effector box: lower and upper must be finite with lower <= upper")
         return self
+
+    @property
+    def n_state_rows(self):
+        """State rows per knot 1..N-1: collision pairs, projectile rows, then the six end-effector box rows."""
+        return len(self.pair_a) + len(self.proj_sph) + (6 if self.ee_box else 0)
 
 
 def contacts_from_fixture(arr):

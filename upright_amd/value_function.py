@@ -50,7 +50,7 @@ def riccati_value_function(P, xs, us, lin, sol, E, Df, rho_N=1e-6, rho_prox=1e-6
     nq, nx, nu, N, h = P.nq, P.nx, P.nu, P.N, P.dt
     ne, nfc = 6 * P.nb, P.nf * P.nc
     npoly = E.shape[0]
-    no = len(P.pair_a) + len(P.proj_sph)
+    no = len(P.pair_a) + len(P.proj_sph) + (6 if getattr(P, "ee_box", False) else 0)   # state rows: pairs, projectile, end-effector box
     o = record_layout(P)
     A, Bq = _dynamics(nq, h)
     Bf = np.hstack([Bq, np.zeros((nx, nfc))])                      # forces do not enter the dynamics
