@@ -306,6 +306,9 @@ int upr_batch_kernel_times(upr_batch* h, double* ms, int* launches);
 int upr_batch_enable_timing(upr_batch* h, int on);
 /* name of the QP kernel instantiation this handle launches (as rocprofv3 prints it): bench.py's roofline.kernel */
 const char* upr_batch_qp_kernel_name(const upr_batch* h);
+/* name of the line-search kernel instantiation the handle's last line-search launch ran (upr_linesearch_kernel<NQ, NT, NFM, NBM,
+ * EXACT, OBS, STAGE>, as rocprofv3 prints it); "" before the first advance */
+const char* upr_batch_ls_kernel_name(upr_batch* h);
 int upr_batch_device(const upr_batch* h);   /* the HIP device the handle lives on; -1 for a null handle */
 /* doubles of device workspace per instance (QP result, multipliers, the QP kernel's far arrays): what an instance writes once and
  * re-streams every interior-point iteration -- bench.py's model of the compulsory DRAM traffic of a launch */

@@ -14,6 +14,7 @@
 #include "../../upright_amd/csrc/upr_qp.h"
 #include "../../upright_amd/csrc/upr_qp2.h"
 #include "../../upright_amd/csrc/upr_qp3.h"
+#include "../../upright_amd/csrc/upr_qp3_list.h"
 
 template <int NQ, bool ORI>
 static void lin_all_o(const upr_lin_args& A);
@@ -179,6 +180,37 @@ long emu_qp3(const upr_problem* P, int B, const double* xs, const double* us, co
 #undef EMU_QP3N
     return -1;
 }
+// The production QP kernel's body for EXACTLY the instantiation cfg = (nq, nb, nc, nf, N, ROWS, SOFT, DENSE) -- at NT = 1, one thread
+// per workgroup -- whichever instantiation the engine would pick for P.  The entries are the library's own list (upr_qp3_list.h:
+// UPR_QP3_PART0, UPR_QP3_EXTRA) expanded here, plus EMU_QP3_RUN_TIME: shapes that tests run through the run-time instantiation.
+// ws == NULL: returns the per-instance workspace (doubles) the instantiation needs (P may be NULL then); -1: cfg is not an entry;
+// -2: P does not have cfg's shape.
+#define EMU_QP3_RUN_TIME(X) X(9, 1, 4, 3, 12, false, false, false)
+long emu_qp3_cfg(const int* cfg, const upr_problem* P, int B, const double* xs, const double* us, const double* x0, const double* lin,
+                 const double* Df, double* ws, long ws_stride, double* stats) {
+    upr_qp_args A;
+    A.P = P; A.xs = xs; A.us = us; A.x0 = x0; A.lin = lin; A.Df = Df; A.ws = ws; A.stats = stats; A.prof = nullptr;
+#define EMU_X(a, b, c, e, n, rows, sf, dense) \
+    if (cfg[0] == a && cfg[1] == b && cfg[2] == c && cfg[3] == e && cfg[4] == n && cfg[5] == (int)rows && cfg[6] == (int)sf && cfg[7] == (int)dense) { \
+        typedef upr_qp3_cfg<a, b, c, e, n, 1, rows, sf, dense> C; \
+        if (!ws) return (long)upr_qp3_ws<C>::total; \
+        if (!P || P->nq != a || P->nb != b || P->nc != c || P->nf != e || P->N != n) return -2; \
+        A.d = upr_make_dims(P); \
+        if (A.d.no > 0 && !rows) return -2; \
+        A.d.ws_stride = (int)ws_stride; \
+        upr_ctx ctx; ctx.tid = 0; ctx.nt = 1; \
+        std::vector<double> L(upr_qp3_lds<C>::total + 16, std::nan("")); \
+        for (int bb = 0; bb < B; ++bb) upr_qp3_solve<C>(ctx, A, bb, L.data()); \
+        return 0; }
+#define EMU_Y(nt, rows) EMU_X(9, 1, 4, 3, 20, rows, false, false)
+    UPR_QP3_PART0(EMU_Y)
+    UPR_QP3_EXTRA(EMU_X)
+    EMU_QP3_RUN_TIME(EMU_X)
+#undef EMU_Y
+#undef EMU_X
+    return -1;
+}
+
 long emu_qp3_lds_doubles() { return (long)upr_qp3_lds<upr_qp3_cfg<9, 1, 4, 3, 20, 256>>::total; }
 
 // production kernel body; returns the per-instance workspace size it needs (doubles) when ws == NULL

@@ -45,7 +45,7 @@ class StandInEngine:
         return dict(qp_status_last=np.zeros(self.B), qp_iters_last=np.full(self.B, 10.0), constraint_violation=np.zeros(self.B))
 
     def kernel_times(self):
-        return dict(linearize_ms=0.0, qp_ms=0.0, linesearch_ms=0.0, launches=[0, 0, 0], qp_kernel="stand-in")
+        return dict(linearize_ms=0.0, qp_ms=0.0, linesearch_ms=0.0, launches=[0, 0, 0], qp_kernel="stand-in", ls_kernel="stand-in")
 
     def copy_policy_device(self, up):
         import ctypes

@@ -605,3 +605,54 @@ def test_paper_arrangement_shapes_production_kernel_source(arrangements, name):
         assert stats[b, 1] == 6 == so.qp_iters_last
         assert np.abs(dx[b] - dxo).max() < 1e-7 * max(1, np.abs(dxo).max())
         assert np.abs(du[b] - duo).max() < 1e-7 * max(1, np.abs(duo).max())
+
+
+def _listed_qp3_instantiations():
+    """(nq, nb, nc, nf, N, ROWS, SOFT, DENSE) of every instantiation of the production QP kernel that libupright_mi carries: the
+    non-experiment branch of upr_qp3_list.h, UPR_QP3_PART0 (the headline, Y(NT, ROWS): upr_qp3_inst.hip fixes the rest) to
+    UPR_QP3_PART{NPARTS - 1}."""
+    import re
+    text = (Path(__file__).resolve().parents[1] / "upright_amd" / "csrc" / "upr_qp3_list.h").read_text().replace("\\\n", " ")
+    branch = text.split("#else", 1)[1].split("#endif", 1)[0]          # (the #if / #elif branches above it are experiments)
+    nparts = int(re.search(r"#define\s+UPR_QP3_NPARTS\s+(\d+)", branch).group(1))
+    flag = {"true": True, "false": False}
+    out = []
+    y = re.search(r"#define\s+UPR_QP3_PART0\(Y\)(.*)", text).group(1)
+    out += [(9, 1, 4, 3, 20, flag[rows], False, False) for _, rows in re.findall(r"Y\(\s*(\d+)\s*,\s*(true|false)\s*\)", y)]
+    extra = re.search(r"#define\s+UPR_QP3_EXTRA\(X\)(.*)", branch).group(1)
+    assert all(w == "UPR_QP3_PART%d(X)" % (k + 1) for k, w in enumerate(extra.split())), extra   # the parts and nothing else
+    for k in range(1, nparts):
+        body = re.search(r"#define\s+UPR_QP3_PART%d\(X\)(.*)" % k, branch).group(1)
+        for t in re.findall(r"X\(([^)]*)\)", body):
+            v = [w.strip() for w in t.split(",")]
+            out.append(tuple(int(w) for w in v[:5]) + tuple(flag[w] for w in v[5:]))
+    return out
+
+
+def test_every_qp_instantiation_has_a_screen_case():
+    """Coverage guard of tests/test_gpu_qp_screen.py: every instantiation of upr_qp3_list.h has a case in its table, and the
+    emulation's exact-instantiation entry (emu_qp3_cfg) has every one of them and every run-time shape the table uses -- an
+    instantiation added to the list without a screen fails here, before any GPU time."""
+    import sys
+    sys.path.insert(0, str(Path(__file__).resolve().parent))
+    from test_gpu_qp_screen import CASES, RUN_TIME_HEADLINE
+
+    listed = _listed_qp3_instantiations()
+    assert len(listed) == len(set(listed)) and len(listed) >= 13, listed
+    missing = [t for t in listed if t not in CASES]
+    assert not missing, "instantiations without a fixed-iteration screen case: %s" % missing
+    run_time = [t for t, (_, _, jit) in CASES.items() if jit is not None]
+    assert set(CASES) == set(listed) | set(run_time) and run_time and RUN_TIME_HEADLINE in listed
+    E = C.CDLL(str(EMU))
+    E.emu_qp3_cfg.restype = C.c_long
+    for t in list(CASES):
+        need = E.emu_qp3_cfg((C.c_int * 8)(*[int(v) for v in t]), None, 1, None, None, None, None, None, None, C.c_long(0), None)
+        assert need > 0, (t, need)
+    assert E.emu_qp3_cfg((C.c_int * 8)(9, 1, 4, 3, 21, 0, 0, 0), None, 1, None, None, None, None, None, None, C.c_long(0), None) == -1
+    # ... and the line-search table of tests/test_gpu_linesearch.py reaches all four forms of launch_linesearch
+    from test_gpu_linesearch import DEVICE_CASES, GOLDEN_LS
+    from test_ls_reference import EXACT, EXACT_ROWS, LARGE, SMALL, ls_case
+    import json
+    arr = json.load(open(Path(__file__).resolve().parent / "golden" / "arrangements.json"))
+    forms = {GOLDEN_LS[n][1] if n in GOLDEN_LS else ls_case(arr, n)["form"] for n in DEVICE_CASES}
+    assert forms == {EXACT, EXACT_ROWS, SMALL, LARGE}, forms

@@ -144,11 +144,8 @@ def test_qp_step_fixed_iterations(arrangements):
 def test_qp_kernel_vs_host_emulation(arrangements, kernel, nt, monkeypatch):
     """Race / indexing screen: the SAME kernel source compiled for the host (tests/emu, one thread per
     workgroup) is fed the GPU's own linearisation records, so any difference beyond summation order is
-    a synchronisation or indexing defect of the GPU execution.  Fixed 8 IPM iterations (tol = 0)."""
-    import ctypes as C
-    from pathlib import Path
-    from upright_amd import _capi
-
+    a synchronisation or indexing defect of the GPU execution.  Fixed 8 IPM iterations (tol = 0).  (Every instantiation of the
+    production kernel, this case among them, is screened at the one it ran: tests/test_gpu_qp_screen.py.)"""
     monkeypatch.setenv("UPR_QP_KERNEL", kernel)
     monkeypatch.setenv("UPR_QP_NT", nt)
     B = 6
@@ -159,19 +156,7 @@ def test_qp_kernel_vs_host_emulation(arrangements, kernel, nt, monkeypatch):
     mpc.set_guess(xs0, us0)
     dxs, dus = mpc.qp_step()
     lin = mpc.lin_records()
-    E = C.CDLL(str(Path(__file__).resolve().parent / "emu" / "libupr_emu.so"))
-    E.emu_qp3.restype = C.c_long
-    cp = _capi.problem_to_c(P)
-    need = E.emu_qp3(C.byref(cp), B, None, None, None, None, None, None, C.c_long(0), None)
-    ws = np.zeros((B, need)); stats = np.zeros((B, 12))
-    bp = np.ascontiguousarray(np.broadcast_to(P.body_params, (B,) + P.body_params.shape))
-    Df = np.zeros((B, 6 * P.nb, P.nf * P.nc))
-    E.emu_make_Df(C.byref(cp), B, _capi.ptr(bp), _capi.ptr(Df))
-    xs0 = np.ascontiguousarray(xs0); us0 = np.ascontiguousarray(us0)
-    assert E.emu_qp3(C.byref(cp), B, _capi.ptr(xs0), _capi.ptr(us0), _capi.ptr(x0), _capi.ptr(lin), _capi.ptr(Df),
-                     _capi.ptr(ws), C.c_long(need), _capi.ptr(stats)) == 0
-    n1 = P.N + 1
-    dxe = ws[:, :n1 * P.nx].reshape(B, n1, P.nx); due = ws[:, n1 * P.nx:n1 * P.nx + P.N * P.nu].reshape(B, P.N, P.nu)
+    dxe, due, _ = _emu_qp3(P, B, x0, xs0, us0, lin, np.broadcast_to(P.body_params, (B,) + P.body_params.shape))
     # a race shows up at 1e-3 and above; 1e-8 leaves room for FMA contraction / rsqrt rounding differences
     assert np.abs(dxs - dxe).max() < 1e-8 * max(1.0, np.abs(dxe).max())
     assert np.abs(dus - due).max() < 1e-8 * max(1.0, np.abs(due).max())
@@ -1771,11 +1756,12 @@ def test_headline_batch_iteration_counts_equal_the_oracles():
     mpc.close()
 
 
-def test_longest_first_dispatch_only_permutes_the_workgroups(arrangements, monkeypatch):
+@pytest.mark.parametrize("B", [192, 193, 2053])
+def test_longest_first_dispatch_only_permutes_the_workgroups(arrangements, monkeypatch, B):
     """From the second QP launch of a handle on, workgroup i solves the instance with the i-th largest iteration count of
     the previous launch (ranked by the line-search launch, upr_linesearch.h order_out).  That is scheduling only: trajectories, gains and statistics are
-    bitwise those of the plain launch order."""
-    B = 192
+    bitwise those of the plain launch order.  The rank reads the B one-byte keys four at a time, 4 x 128 words per trip of its
+    loop, and the last B % 4 one by one: B = 193 reaches that tail, B = 2053 a second trip and the tail."""
     P, x0, way = _setup(arrangements, B, seed=71, use_feedback_policy=True)
     out = {}
     for on in ("1", "0"):

@@ -296,6 +296,8 @@ struct upr_batch {
     std::vector<double> held_stats; std::vector<unsigned char> held_keys;   // upr_batch_hold_stats
     std::vector<double> kkt_slack;   // slacks of the rows at the exit of the last upr_batch_qp_kkt ([B][N+1][ni]; upr_batch_qp_slacks)
     std::string qp_name;   // the QP kernel instantiation this handle launches
+    std::string ls_name;   // the line-search kernel instantiation of the handle's last line-search launch (upr_batch_ls_kernel_name)
+    int ls_form[5] = {0, 0, 0, 0, -1};   // (NFM, NBM, EXACT, OBS, STAGE) of that launch; STAGE -1: no line search launched yet
     std::vector<hipEvent_t> ev_pool, ev_free;   // events in use (pairs, in launch order) / harvested ones waiting for reuse
     std::vector<int> ev_slot;
 };
@@ -735,19 +737,22 @@ int launch_linesearch(upr_batch* h, const upr_ls_args& A0) {
     // two waves per instance (wave 0: the chain walks of a trial, wave 1: its flat sums): 241 registers, four workgroups per CU by
     // LDS.  Four waves (more flat lanes, 128 registers a lane for four workgroups per CU: 135 spilled) measured 48 against 33 us.
     const int nt = 128;
-    auto launch = [&](void (*kern)(upr_ls_args)) {
+    // (nfm, nbm, exact, obs: the template arguments of kern besides NQ, NT and STAGE, remembered for upr_batch_ls_kernel_name)
+    auto launch = [&](void (*kern)(upr_ls_args), int nfm, int nbm, bool exact, bool obs) {
         if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(h->B), dim3(nt), lds, h->stream, A);
+        h->ls_form[0] = nfm; h->ls_form[1] = nbm; h->ls_form[2] = exact; h->ls_form[3] = obs; h->ls_form[4] = A.stage_full != 0;
     };
     // small shapes (one body, up to four frictional contacts): per-lane vectors sized for them
     // exactly the headline's contact structure (one body on the tray, four frictional contacts): every bound a constant
     const bool st = A.stage_full != 0;   // (compile-time in the kernel: its staged arrays are LDS pointers, not generic ones)
-    if (h->d.nfc == 12 && h->d.nb == 1 && h->P.nf == 3 && h->P.nc == 4 && h->d.no == 0) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, true, false, true> : upr_linesearch_kernel<NQ, 128, 12, 1, true, false, false>);
+    if (h->d.nfc == 12 && h->d.nb == 1 && h->P.nf == 3 && h->P.nc == 4 && h->d.no == 0) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, true, false, true> : upr_linesearch_kernel<NQ, 128, 12, 1, true, false, false>, 12, 1, true, false);
     // ... the same with state rows: collision / projectile rows (configs[4], the obstacle experiments: round 5), the end-effector box
     // (a box-only problem skips the sphere walk: upr_ls_knot)
-    else if (h->d.nfc == 12 && h->d.nb == 1 && h->P.nf == 3 && h->P.nc == 4) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, true, true, true> : upr_linesearch_kernel<NQ, 128, 12, 1, true, true, false>);
-    else if (h->d.nfc <= 12 && h->d.nb == 1) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, false, true, true> : upr_linesearch_kernel<NQ, 128, 12, 1, false, true, false>);
-    else launch(st ? upr_linesearch_kernel<NQ, 128, 3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true, true> : upr_linesearch_kernel<NQ, 128, 3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true, false>);
+    else if (h->d.nfc == 12 && h->d.nb == 1 && h->P.nf == 3 && h->P.nc == 4) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, true, true, true> : upr_linesearch_kernel<NQ, 128, 12, 1, true, true, false>, 12, 1, true, true);
+    else if (h->d.nfc <= 12 && h->d.nb == 1) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, false, true, true> : upr_linesearch_kernel<NQ, 128, 12, 1, false, true, false>, 12, 1, false, true);
+    else launch(st ? upr_linesearch_kernel<NQ, 128, 3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true, true> : upr_linesearch_kernel<NQ, 128, 3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true, false>,
+                3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true);
     UPR_HIP(hipGetLastError());
     return 0;
 }
@@ -1165,6 +1170,15 @@ static int get_feedback_core(upr_batch* h, double* K) {
 double upr_batch_last_solve_ms(const upr_batch* h) { return h ? h->last_ms : 0.0; }
 
 const char* upr_batch_qp_kernel_name(const upr_batch* h) { return h ? h->qp_name.c_str() : ""; }
+
+const char* upr_batch_ls_kernel_name(upr_batch* h) {
+    if (!h || h->ls_form[4] < 0) return "";
+    const int* f = h->ls_form;
+    char buf[128];
+    snprintf(buf, sizeof(buf), "upr_linesearch_kernel<%d, 128, %d, %d, %s, %s, %s>", h->P.nq, f[0], f[1], f[2] ? "true" : "false", f[3] ? "true" : "false", f[4] ? "true" : "false");
+    h->ls_name = buf;
+    return h->ls_name.c_str();
+}
 
 /* restore == 0: keep a copy of the per-instance statistics and of the QP dispatch keys of the last advance; restore != 0: put that
  * copy back.  Brackets a query that solves one more QP on the handle (upr_batch_qp_kkt behind valueFunction): afterwards
