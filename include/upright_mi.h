@@ -291,6 +291,30 @@ int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double*
  * stateInputEqualityConstraintLagrangian, upright_control/src/pybindings.cpp:398-412 (ocs2 getValueFunction = the Riccati
  * cost-to-go of the last QP, HPIPM's barrier-augmented P_k) -- are served from (upright_amd/value_function.py). */
 int upr_batch_qp_slacks(upr_batch* h, double* t);
+/* Slack pairs of the softened rows of that QP (HPIPM slacks, `soft_*` above): sigma[B][N+1][ni] the slack variable of the row (cost
+ * 1/2 Z sigma^2 + z sigma), tau and gam the slack and the multiplier of sigma >= 0, slot order of lam; sigma = 0, tau = 1, gam = 0 in slots
+ * that are not softened rows of the knot.  The kernels factor such a row with the weight w0 (Z + gam / tau) / (Z + w0 + gam / tau),
+ * w0 = lam / t.  Same lifetime as upr_batch_qp_slacks; any pointer may be NULL. */
+int upr_batch_qp_slack_pairs(upr_batch* h, double* sigma, double* tau, double* gam);
+
+/* ------------------------------------------------------------------------------------------------
+ * Value function of the last QP for the whole batch (ControllerInterface.valueFunction / valueFunctionStateDerivative,
+ * upright_control/src/pybindings.cpp:398-402 -> ocs2 getValueFunction: the Riccati cost-to-go of the solver's last QP), on the device.
+ *   upr_batch_value_function_update  linearises at the current plan, solves one QP there with the multiplier export and runs the
+ *       cost-to-go kernel (upright_amd/csrc/upr_value.h): P_k, p_k, J_k and the expansion points X_k of every instance and knot stay
+ *       in device memory.  Softened inequality rows enter with the weight above, a softened equality with S = Df Hff^-1 Df' + I / Z.
+ *       Statistics and QP dispatch keys of the last advance are put back afterwards (as upr_batch_hold_stats does).  Not available
+ *       with dynamic obstacles.
+ *   upr_batch_value_function  V[n] and dVdx[n][nx] at n points (inst[n], t[n], x[n][nx]):
+ *       V(t, x) = J + p'(x - X) + 1/2 (x - X)'P (x - X),  dV/dx = p + P (x - X), of the two knots around t, interpolated linearly in t
+ *       (t is clamped to the plan's horizon).  Fails before the first update, and with "stale" once the plan or the observation
+ *       changed since the update (advance, tick, reset, set_guess, set_observation).
+ *   upr_batch_get_cost_to_go  Pk[B][N+1][nx][nx], pk[B][N+1][nx], J[B][N+1], X[B][N+1][nx]; any pointer may be NULL.
+ *   upr_batch_value_function_ms  device time (ms) of the last cost-to-go launch, HIP events around that launch only. */
+int upr_batch_value_function_update(upr_batch* h);
+int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double* t, const double* x, double* V, double* dVdx);
+int upr_batch_get_cost_to_go(upr_batch* h, double* Pk, double* pk, double* J, double* X);
+double upr_batch_value_function_ms(const upr_batch* h);
 
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):
  * xs (B*(N+1)*nx doubles) and us (B*N*nu doubles) */

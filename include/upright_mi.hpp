@@ -86,6 +86,16 @@ class ControllerInterface {
         return s;
     }
     double last_solve_ms() const { return upr_batch_last_solve_ms(h_); }
+    // valueFunction / valueFunctionStateDerivative for n points at once (instance, time and state of each): the cost-to-go of the QP
+    // at the current plan is rebuilt on the device when `update` is set (after every advance), then evaluated; V[n], dVdx[n][nx]
+    void value_function(const std::vector<int>& inst, const std::vector<double>& t, const std::vector<double>& x, std::vector<double>& V,
+                        std::vector<double>& dVdx, bool update = true) {
+        const int n = (int)inst.size();
+        if ((int)t.size() != n || (int)x.size() != n * nx_) throw std::runtime_error("t must hold n and x n * nx values");
+        if (update) check(upr_batch_value_function_update(h_));
+        V.assign((size_t)n, 0.0); dVdx.assign((size_t)n * nx_, 0.0);
+        check(upr_batch_value_function(h_, n, inst.data(), t.data(), x.data(), V.data(), dVdx.data()));
+    }
     upr_batch* handle() { return h_; }
 
    private:

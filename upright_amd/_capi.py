@@ -146,6 +146,11 @@ PROTOTYPES = [
     ("upr_batch_qp_step", C.c_int, [C.c_void_p, dp, dp]),
     ("upr_batch_qp_kkt", C.c_int, [C.c_void_p, dp, dp, dp, dp, dp, dp, ip]),
     ("upr_batch_qp_slacks", C.c_int, [C.c_void_p, dp]),
+    ("upr_batch_qp_slack_pairs", C.c_int, [C.c_void_p, dp, dp, dp]),
+    ("upr_batch_value_function_update", C.c_int, [C.c_void_p]),
+    ("upr_batch_value_function", C.c_int, [C.c_void_p, C.c_int, ip, dp, dp, dp, dp]),
+    ("upr_batch_get_cost_to_go", C.c_int, [C.c_void_p, dp, dp, dp, dp]),
+    ("upr_batch_value_function_ms", C.c_double, [C.c_void_p]),
     ("upr_batch_device_ptrs", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("upr_batch_kernel_times", C.c_int, [C.c_void_p, dp, ip]),
     ("upr_batch_enable_timing", C.c_int, [C.c_void_p, C.c_int]),

@@ -30,6 +30,7 @@
 #include "upr_qp3.h"
 #include "upr_qp3_list.h"
 #include "upr_qp3_launch.h"
+#include "upr_value.h"
 
 namespace {
 
@@ -295,6 +296,13 @@ struct upr_batch {
     std::vector<double> hDf;
     std::vector<double> held_stats; std::vector<unsigned char> held_keys;   // upr_batch_hold_stats
     std::vector<double> kkt_slack;   // slacks of the rows at the exit of the last upr_batch_qp_kkt ([B][N+1][ni]; upr_batch_qp_slacks)
+    std::vector<double> kkt_pairs;   // slack pairs of the softened rows of that QP, [3: sigma, tau, gam][B][N+1][ni] (upr_batch_qp_slack_pairs)
+    // value function of the last QP (upr_batch_value_function_update): cost-to-go matrices, gradients, cost-to-go of the plan and
+    // expansion points of every instance on the device, and the time of knot 0 of the plan they belong to
+    double *vf_P = nullptr, *vf_p = nullptr, *vf_J = nullptr, *vf_X = nullptr, *vf_t0 = nullptr;
+    int vf_state = 0;        // 0: no update yet; 1: current; 2: stale (the plan or the observation changed since)
+    double vf_ms = 0.0;      // device time of the last cost-to-go launch
+    hipEvent_t vf_ev[2] = {nullptr, nullptr};
     std::string qp_name;   // the QP kernel instantiation this handle launches
     std::string ls_name;   // the line-search kernel instantiation of the handle's last line-search launch (upr_batch_ls_kernel_name)
     int ls_form[5] = {0, 0, 0, 0, -1};   // (NFM, NBM, EXACT, OBS, STAGE) of that launch; STAGE -1: no line search launched yet
@@ -836,6 +844,7 @@ upr_fb_src fb_source(const upr_batch* h) {
 // line-search launch that follows the QP (upr_linesearch.h, order_out): it only permutes which workgroup solves which instance.
 int advance_impl(upr_batch* h) {
     const upr_dims& d = h->d;
+    if (h->vf_state) h->vf_state = 2;
     if (!h->guess_set) {
         hipLaunchKernelGGL(prepare_kernel, dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->B, h->has_prev ? 1 : 0, h->tprev,
                            h->xs_prev, h->us_prev, h->t0, h->x0, h->xs, h->us, h->stats, h->done);
@@ -1032,6 +1041,8 @@ void upr_batch_destroy(upr_batch* h) {
     if (h->pflag) hipFree(h->pflag);
     hipFree(h->xs_prev); hipFree(h->us_prev); hipFree(h->tprev); hipFree(h->lin); hipFree(h->Df); hipFree(h->ws); hipFree(h->stats);
     hipFree(h->done); hipFree(h->order); hipFree(h->iter_key); if (h->pin) (void)hipHostFree(h->pin); if (h->tick_exec) (void)hipGraphExecDestroy(h->tick_exec); hipFree(h->prof); hipFree(h->kkt);
+    hipFree(h->vf_P); hipFree(h->vf_p); hipFree(h->vf_J); hipFree(h->vf_X); hipFree(h->vf_t0);
+    for (hipEvent_t e : h->vf_ev) if (e) (void)hipEventDestroy(e);
     hipFree(h->ev_t); hipFree(h->ev_xo); hipFree(h->ev_x) /* (ev_u: same block) */;
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
@@ -1045,6 +1056,7 @@ int upr_batch_reset(upr_batch* h, const double* way_p) {
     h->has_prev = false;
     UPR_HIP(hipStreamSynchronize(h->stream));
     h->guess_set = false;
+    if (h->vf_state) h->vf_state = 2;
     return 0;
 }
 
@@ -1064,6 +1076,7 @@ int upr_batch_set_target_orientations(upr_batch* h, const double* way_q) {
 
 static int set_observation_core(upr_batch* h, const double* t, int t_stride, const double* x) {
     UPR_ENTER(h);
+    if (h->vf_state) h->vf_state = 2;
     std::vector<double> tt(h->B);
     for (int b = 0; b < h->B; ++b) tt[b] = t[(size_t)b * (t_stride ? 1 : 0)];
     UPR_HIP(hipMemcpyAsync(h->t0, tt.data(), sizeof(double) * h->B, hipMemcpyHostToDevice, h->stream));
@@ -1074,6 +1087,7 @@ static int set_observation_core(upr_batch* h, const double* t, int t_stride, con
 
 static int set_guess_core(upr_batch* h, const double* xs, const double* us) {
     UPR_ENTER(h);
+    if (h->vf_state) h->vf_state = 2;
     const upr_dims& d = h->d;
     UPR_HIP(hipMemcpyAsync(h->xs, xs, sizeof(double) * h->B * (d.N + 1) * d.nx, hipMemcpyHostToDevice, h->stream));
     UPR_HIP(hipMemcpyAsync(h->us, us, sizeof(double) * h->B * d.N * d.nu, hipMemcpyHostToDevice, h->stream));
@@ -1309,6 +1323,20 @@ int upr_batch_eq_input_jacobian(upr_batch* h, int inst, double* gu) {
     return 0;
 }
 
+// does the QP kernel of this handle carry slack pairs (sigma, tau, gam) of softened inequality rows, and where: the SOFT
+// instantiations of the production kernel export them behind the slacks, the generic kernel keeps them in the instance workspace
+static bool vf_has_pairs(const upr_batch* h) { return h->d.soft && (h->use_qp3 ? needs_soft(h->P, h->d) : !h->use_qp2); }
+
+// linearise at the current trajectory and solve one QP there with the multiplier export (no synchronisation)
+static int kkt_launch(upr_batch* h) {
+    const int kdoubles = upr_kkt_doubles(h->d);
+    if (h->use_qp3 && !h->kkt && dev_alloc(&h->kkt, (size_t)h->B * kdoubles)) return 1;
+    if (do_linearize(h, traj_lin_args(h))) return 1;
+    upr_qp_args A = make_qp_args(h);
+    if (h->use_qp3) { A.kkt = h->kkt; A.kkt_stride = kdoubles; }
+    return launch_qp(h, A);
+}
+
 static int qp_step_core(upr_batch* h, double* dxs, double* dus) {
     UPR_ENTER(h);
     const upr_dims& d = h->d;
@@ -1335,11 +1363,7 @@ int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double*
     const upr_dims& d = h->d;
     if (ni_out) *ni_out = d.ni_stage;
     const int kdoubles = upr_kkt_doubles(d);
-    if (h->use_qp3 && !h->kkt && dev_alloc(&h->kkt, (size_t)h->B * kdoubles)) return 1;
-    if (do_linearize(h, traj_lin_args(h))) return 1;
-    upr_qp_args A = make_qp_args(h);
-    if (h->use_qp3) { A.kkt = h->kkt; A.kkt_stride = kdoubles; }
-    if (launch_qp(h, A)) return 1;
+    if (kkt_launch(h)) return 1;
     UPR_HIP(hipStreamSynchronize(h->stream));
     std::vector<double> ws((size_t)h->B * d.ws_stride), kk;
     UPR_HIP(hipMemcpy(ws.data(), h->ws, sizeof(double) * ws.size(), hipMemcpyDeviceToHost));
@@ -1356,11 +1380,23 @@ int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double*
         if (dxs) std::memcpy(dxs + (size_t)b * n1 * d.nx, w + d.ws_dx, sizeof(double) * n1 * d.nx);
         if (dus) std::memcpy(dus + (size_t)b * d.N * d.nu, w + d.ws_du, sizeof(double) * d.N * d.nu);
         const double *spi, *snu, *sy, *sl, *st;
-        if (h->use_qp3) { const double* k = kk.data() + (size_t)b * kdoubles; spi = k; snu = spi + n1 * d.nx; sy = snu + d.N * d.ne; sl = sy + d.neN; st = sl + (size_t)n1 * d.ni_stage; }
-        else { spi = w + o_pi; snu = w + o_nu; sy = w + o_y; sl = w + o_lam; st = w + o_t; }
-        if (b == 0) h->kkt_slack.assign((size_t)h->B * n1 * d.ni_stage, 1.0);
+        const size_t nsl = (size_t)n1 * d.ni_stage;
+        const double* sp[3] = {nullptr, nullptr, nullptr};   // sigma, tau, gam of the softened rows (problems that have some)
+        if (h->use_qp3) { const double* k = kk.data() + (size_t)b * kdoubles; spi = k; snu = spi + n1 * d.nx; sy = snu + d.N * d.ne; sl = sy + d.neN; st = sl + nsl;
+                          if (vf_has_pairs(h)) for (int q = 0; q < 3; ++q) sp[q] = st + (q + 1) * nsl; }
+        else { spi = w + o_pi; snu = w + o_nu; sy = w + o_y; sl = w + o_lam; st = w + o_t;
+               if (vf_has_pairs(h)) { sp[0] = w + d.ws_sig; sp[1] = w + d.ws_tau; sp[2] = w + d.ws_gam; } }
+        if (b == 0) {
+            h->kkt_slack.assign((size_t)h->B * nsl, 1.0);
+            h->kkt_pairs.assign(3 * (size_t)h->B * nsl, 0.0);
+            std::fill(h->kkt_pairs.begin() + (size_t)h->B * nsl, h->kkt_pairs.begin() + 2 * (size_t)h->B * nsl, 1.0);   // (sigma 0, tau 1, gam 0 where a slot is not a softened row)
+        }
         for (int k = 0; k < n1; ++k) for (int j = 0; j < d.ni_stage; ++j)
-            if (upr_ineq_active(d, k, j)) h->kkt_slack[((size_t)b * n1 + k) * d.ni_stage + j] = st[(size_t)k * d.ni_stage + j];
+            if (upr_ineq_active(d, k, j)) {
+                const size_t e = ((size_t)b * n1 + k) * d.ni_stage + j;
+                h->kkt_slack[e] = st[(size_t)k * d.ni_stage + j];
+                if (sp[0] && upr_slot_soft(&h->P, d, j)) for (int q = 0; q < 3; ++q) h->kkt_pairs[q * (size_t)h->B * nsl + e] = sp[q][(size_t)k * d.ni_stage + j];
+            }
         if (pi) std::memcpy(pi + (size_t)b * n1 * d.nx, spi, sizeof(double) * n1 * d.nx);
         if (nu) std::memcpy(nu + (size_t)b * d.N * d.ne, snu, sizeof(double) * d.N * d.ne);
         if (yN && d.neN) std::memcpy(yN + (size_t)b * d.neN, sy, sizeof(double) * d.neN);
@@ -1382,6 +1418,118 @@ int upr_batch_qp_slacks(upr_batch* h, double* t) {
     if (t) std::memcpy(t, h->kkt_slack.data(), sizeof(double) * h->kkt_slack.size());
     return 0;
 }
+
+/* The slack pairs of the softened rows of that QP: sigma (the row's slack variable, cost 1/2 Z sigma^2 + z sigma), tau and gam (the
+ * slack and the multiplier of sigma >= 0), each [B][N+1][ni] in the slot order of lam; sigma = 0, tau = 1, gam = 0 in slots that are
+ * not softened rows of the knot.  A softened row is factored with the weight w0 (Z + gam / tau) / (Z + w0 + gam / tau), w0 = lam / t.
+ * Any pointer may be NULL. */
+int upr_batch_qp_slack_pairs(upr_batch* h, double* sigma, double* tau, double* gam) {
+    UPR_ENTER(h);
+    if (h->kkt_pairs.empty()) return fail("upr_batch_qp_slack_pairs: no upr_batch_qp_kkt call on this handle yet");
+    const size_t n = h->kkt_pairs.size() / 3;
+    double* out[3] = {sigma, tau, gam};
+    for (int q = 0; q < 3; ++q) if (out[q]) std::memcpy(out[q], h->kkt_pairs.data() + q * n, sizeof(double) * n);
+    return 0;
+}
+
+/* ---- value function of the last QP, batched (upr_value.h) ---- */
+int upr_batch_value_function_update(upr_batch* h) {
+    UPR_ENTER(h);
+    if (h->P.n_dyn) return fail("upr_batch_value_function_update: not available with a dynamic obstacle (interface states)");
+    if (!h->has_prev && !h->guess_set) return fail("upr_batch_value_function_update: no plan on this handle yet (advance or set a guess first)");
+    const upr_dims& d = h->d;
+    const size_t B = (size_t)h->B, n1 = (size_t)d.N + 1, nx = (size_t)d.nx;
+    const size_t lds = (size_t)upr_vf_lds_layout(d).total * sizeof(double);
+    if (lds > 160 * 1024) return fail("upr_batch_value_function_update: working set exceeds 160 KiB of LDS");
+    if (!h->vf_P) {
+        if (dev_alloc(&h->vf_P, B * n1 * nx * nx) || dev_alloc(&h->vf_p, B * n1 * nx) || dev_alloc(&h->vf_J, B * n1) || dev_alloc(&h->vf_X, B * n1 * nx) || dev_alloc(&h->vf_t0, B)) return 1;
+        UPR_HIP(hipEventCreate(&h->vf_ev[0])); UPR_HIP(hipEventCreate(&h->vf_ev[1]));
+    }
+    h->vf_state = 0;
+    // statistics and dispatch keys of the solve are put back behind the query's QP (what upr_batch_hold_stats does, on a copy of
+    // its own: a caller may hold one across this call)
+    const size_t ns = sizeof(double) * B * UPR_NSTATS, nk = (B + 3) & ~(size_t)3;
+    std::vector<double> st(B * UPR_NSTATS); std::vector<unsigned char> keys(nk);
+    UPR_HIP(hipStreamSynchronize(h->stream));
+    UPR_HIP(hipMemcpy(st.data(), h->stats, ns, hipMemcpyDeviceToHost));
+    UPR_HIP(hipMemcpy(keys.data(), h->iter_key, nk, hipMemcpyDeviceToHost));
+    if (kkt_launch(h)) return 1;
+    upr_vf_args A;
+    A.P = h->dP; A.d = d; A.xs = h->xs; A.us = h->us; A.lin = h->lin; A.Df = h->Df; A.ws = h->ws;
+    const int nsl = (int)n1 * d.ni_stage;
+    if (h->use_qp3) {
+        A.mult = h->kkt; A.mult_stride = upr_kkt_doubles(d);
+        A.o_pi = 0; A.o_nu = (int)(n1 * nx); A.o_lam = A.o_nu + d.N * d.ne + d.neN; A.o_t = A.o_lam + nsl;
+        A.o_sig = A.o_t + nsl; A.o_tau = A.o_sig + nsl; A.o_gam = A.o_tau + nsl;
+    } else {
+        A.mult = h->ws; A.mult_stride = d.ws_stride;
+        A.o_pi = d.ws_pi; A.o_nu = d.ws_nu; A.o_lam = d.ws_lam; A.o_t = d.ws_t; A.o_sig = d.ws_sig; A.o_tau = d.ws_tau; A.o_gam = d.ws_gam;
+        if (h->use_qp2) {
+#define X(a, b, c, e) if (h->P.nq == a && h->P.nb == b && h->P.nc == c && h->P.nf == e) { upr_qp2_ws<upr_qp2_dims<a, b, c, e>> w(d.N, d.neN); A.o_pi = w.pi; A.o_nu = w.nu; A.o_lam = w.lam; A.o_t = w.t; }
+            UPR_QP2_SHAPES(X)
+#undef X
+        }
+    }
+    if (!vf_has_pairs(h)) A.o_sig = A.o_tau = A.o_gam = -1;
+    A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X;
+    if (lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)upr_value_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    UPR_HIP(hipEventRecord(h->vf_ev[0], h->stream));
+    hipLaunchKernelGGL(upr_value_kernel, dim3(h->B), dim3(UPR_VF_NT), lds, h->stream, A);
+    UPR_HIP(hipGetLastError());
+    UPR_HIP(hipEventRecord(h->vf_ev[1], h->stream));
+    UPR_HIP(hipMemcpyAsync(h->vf_t0, h->t0, sizeof(double) * B, hipMemcpyDeviceToDevice, h->stream));
+    UPR_HIP(hipStreamSynchronize(h->stream));
+    float ms = 0.0f;
+    UPR_HIP(hipEventElapsedTime(&ms, h->vf_ev[0], h->vf_ev[1]));
+    h->vf_ms = ms;
+    UPR_HIP(hipMemcpy(h->stats, st.data(), ns, hipMemcpyHostToDevice));
+    UPR_HIP(hipMemcpy(h->iter_key, keys.data(), nk, hipMemcpyHostToDevice));
+    h->vf_state = 1;
+    return 0;
+}
+
+static int vf_ready(const upr_batch* h, const char* who) {
+    if (h->vf_state == 0) return fail(std::string(who) + ": no upr_batch_value_function_update on this handle yet");
+    if (h->vf_state == 2) return fail(std::string(who) + ": the cost-to-go is stale (the plan or the observation changed since upr_batch_value_function_update)");
+    return 0;
+}
+
+int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double* t, const double* x, double* V, double* dVdx) {
+    UPR_ENTER(h);
+    if (vf_ready(h, "upr_batch_value_function")) return 1;
+    if (n <= 0) return 0;
+    if (!inst || !t || !x) return fail("upr_batch_value_function: null argument");
+    const upr_dims& d = h->d;
+    for (int i = 0; i < n; ++i) if (inst[i] < 0 || inst[i] >= h->B) return fail("instance index out of range");
+    DevBuf<int> dinst; DevBuf<double> dt_, dx, dV, dg;
+    if (dinst.alloc(n) || dt_.alloc(n) || dx.alloc((size_t)n * d.nx) || dV.alloc(n) || dg.alloc((size_t)n * d.nx)) return 1;
+    UPR_HIP(hipMemcpy(dinst, inst, sizeof(int) * n, hipMemcpyHostToDevice));
+    UPR_HIP(hipMemcpy(dt_, t, sizeof(double) * n, hipMemcpyHostToDevice));
+    UPR_HIP(hipMemcpy(dx, x, sizeof(double) * n * d.nx, hipMemcpyHostToDevice));
+    upr_vfq_args A;
+    A.d = d; A.dt = h->P.dt; A.n = n; A.inst = dinst; A.t = dt_; A.x = dx; A.t0 = h->vf_t0;
+    A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X; A.V = dV; A.dV = dg;
+    hipLaunchKernelGGL(upr_value_query_kernel, dim3(n), dim3(64), 0, h->stream, A);
+    UPR_HIP(hipGetLastError());
+    UPR_HIP(hipStreamSynchronize(h->stream));
+    if (V) UPR_HIP(hipMemcpy(V, dV, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (dVdx) UPR_HIP(hipMemcpy(dVdx, dg, sizeof(double) * n * d.nx, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int upr_batch_get_cost_to_go(upr_batch* h, double* Pk, double* pk, double* J, double* X) {
+    UPR_ENTER(h);
+    if (vf_ready(h, "upr_batch_get_cost_to_go")) return 1;
+    const size_t B = (size_t)h->B, n1 = (size_t)h->d.N + 1, nx = (size_t)h->d.nx;
+    UPR_HIP(hipStreamSynchronize(h->stream));
+    if (Pk) UPR_HIP(hipMemcpy(Pk, h->vf_P, sizeof(double) * B * n1 * nx * nx, hipMemcpyDeviceToHost));
+    if (pk) UPR_HIP(hipMemcpy(pk, h->vf_p, sizeof(double) * B * n1 * nx, hipMemcpyDeviceToHost));
+    if (J) UPR_HIP(hipMemcpy(J, h->vf_J, sizeof(double) * B * n1, hipMemcpyDeviceToHost));
+    if (X) UPR_HIP(hipMemcpy(X, h->vf_X, sizeof(double) * B * n1 * nx, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+double upr_batch_value_function_ms(const upr_batch* h) { return h ? h->vf_ms : 0.0; }
 
 int upr_batch_device_ptrs(upr_batch* h, void** xs, void** us) {
     UPR_ENTER(h);
@@ -1476,6 +1624,7 @@ int upr_batch_reset_async(upr_batch* h) {
     UPR_ENTER(h);
     h->has_prev = false;
     h->guess_set = false;
+    if (h->vf_state) h->vf_state = 2;
     return 0;
 }
 
@@ -1558,6 +1707,7 @@ int upr_batch_evaluate_policy(upr_batch* h, const double* t, int t_stride, const
 int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x, double* x_out, double* u_out, double* stats_out) {
     UPR_ENTER(h);
     if (!t || !x || !x_out || !u_out) return fail("upr_batch_tick: null argument");
+    if (h->vf_state) h->vf_state = 2;
     const upr_dims& d = h->d;
     const size_t B = (size_t)h->B, nx = (size_t)d.nx, nu = (size_t)d.nu, ndyn = 9 * (size_t)h->P.n_dyn;
     if (!h->ev_t && (dev_alloc(&h->ev_t, h->B) || dev_alloc(&h->ev_xo, B * nx) || dev_alloc(&h->ev_x, B * (nx + nu)))) return 1;

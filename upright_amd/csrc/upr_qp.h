@@ -89,7 +89,9 @@ static UPR_HDI void upr_qp_store_key(const upr_qp_args& A, int b, int it) { if (
 static UPR_HDI int upr_qp_instance(const upr_qp_args& A, int wg) { return A.order ? A.order[wg] : wg; }
 // (round 5: the slacks t of the rows behind their multipliers, same slot layout -- the barrier weights lam / t of the last iterate are
 // what the value function of the QP is built from, upright_amd/value_function.py)
-static inline UPR_HD int upr_kkt_doubles(const upr_dims& d) { return (d.N + 1) * d.nx + d.N * d.ne + d.neN + 2 * (d.N + 1) * d.ni_stage; }
+// (and, for a problem with softened rows only: the slack pairs sigma, tau, gam of those rows behind the slacks, three more blocks of
+// the same slots -- what the factored weight w0 (Z + gam / tau) / (Z + w0 + gam / tau) of a softened row is built from, upr_value.h)
+static inline UPR_HD int upr_kkt_doubles(const upr_dims& d) { return (d.N + 1) * d.nx + d.N * d.ne + d.neN + (d.soft ? 5 : 2) * (d.N + 1) * d.ni_stage; }
 
 // LDS layout (doubles)
 struct upr_qp_lds {

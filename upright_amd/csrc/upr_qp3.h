@@ -3327,6 +3327,11 @@ ftoc(6, 4);   // (-DUPR_QP3_PROF_FLAT=4: the classes of rows of the sweeps -- sl
             UPR_FORT(e, N * NE) K[o_nu + e] = ws[W::nu + e];
             UPR_FORT(q, neN) K[o_y + q] = L[O::yN + q];
             UPR_FORT(e, N1 * ni) { K[o_l + e] = 0.0; K[o_t + e] = 1.0; }
+            // SOFT: the slack pairs of the softened rows behind the slacks (upr_batch_qp_slack_pairs), sigma / tau / gam in three
+            // blocks of the same slots: 0 / 1 / 0 where a slot is not a softened row of the knot
+            const int o_sg = o_t + N1 * ni, o_ta = o_sg + N1 * ni, o_ga = o_ta + N1 * ni;
+            const bool pairs = C::SOFT && A.d.soft;   // (a hard problem on a SOFT instantiation: its export buffer has no such blocks)
+            if (pairs) UPR_FORT(e, N1 * ni) { K[o_sg + e] = 0.0; K[o_ta + e] = 1.0; K[o_ga + e] = 0.0; }
             UPR_SYNC();
             // (the box rows out of their parked copy -- store_rows() behind the last step, or the initial point -- not out of the
             //  registers: an export that keeps (t, lam) alive behind the loop moves the register allocation of the loop itself,
@@ -3352,6 +3357,37 @@ ftoc(6, 4);   // (-DUPR_QP3_PROF_FLAT=4: the classes of rows of the sweeps -- sl
             }
             if (NF == 3) UPR_FORT(e, 5 * C::NCI) { const int ic = e / 5, k = ic / NC, ci = ic % NC, sl = k * ni + 2 * NX + 2 * NU + 5 * ci + e % 5; K[o_l + sl] = G[F::cl + e]; K[o_t + sl] = G[F::ct + e]; }
             if (no > 0) UPR_FORT(e, (N - 1) * no) { const int k = 1 + e / no, r = e % no, sl = k * ni + 2 * NX + 2 * NU + C::NP + r, ei = (k - 1) * UPR_QP3_NOMAX + r; K[o_l + sl] = G[F::ol + ei]; K[o_t + sl] = G[F::ot + ei]; }
+            if (pairs) {   // (out of the parked copies as well: the layout of store_rows / stx / stu, and the far arrays sfr / sor)
+                const double* Q = R + NROWV * NT;
+                if (softx) {
+#pragma unroll
+                    for (int q = 0; q < C::QX; ++q) {
+                        const int ix = tid() + q * NT;
+                        if (ix < C::NXI) for (int s2 = 0; s2 < 2; ++s2) {
+                            const int sl = (1 + ix / NX) * ni + s2 * NX + ix % NX;
+                            K[o_sg + sl] = Q[(6 * q + 3 * s2) * NT]; K[o_ta + sl] = Q[(6 * q + 3 * s2 + 1) * NT]; K[o_ga + sl] = Q[(6 * q + 3 * s2 + 2) * NT];
+                        }
+                    }
+                }
+                if (softu) {
+#pragma unroll
+                    for (int q = 0; q < C::QU; ++q) {
+                        const int iu = tid() + q * NT;
+                        if (iu < C::NUI) for (int s2 = 0; s2 < 2; ++s2) {
+                            const int sl = (iu / NU) * ni + 2 * NX + s2 * NU + iu % NU;
+                            K[o_sg + sl] = Q[(6 * C::QX + 6 * q + 3 * s2) * NT]; K[o_ta + sl] = Q[(6 * C::QX + 6 * q + 3 * s2 + 1) * NT]; K[o_ga + sl] = Q[(6 * C::QX + 6 * q + 3 * s2 + 2) * NT];
+                        }
+                    }
+                }
+                if (NF == 3 && softp) UPR_FORT(e, 5 * C::NCI) {
+                    const int ic = e / 5, sl = (ic / NC) * ni + 2 * NX + 2 * NU + 5 * (ic % NC) + e % 5;
+                    K[o_sg + sl] = G[F::sfr + e]; K[o_ta + sl] = G[F::sfr + F::sfs + e]; K[o_ga + sl] = G[F::sfr + 2 * F::sfs + e];
+                }
+                if (C::ROWS && no > 0 && softp) UPR_FORT(e, (N - 1) * no) {
+                    const int k = 1 + e / no, r = e % no, sl = k * ni + 2 * NX + 2 * NU + C::NP + r, ei = (k - 1) * UPR_QP3_NOMAX + r;
+                    K[o_sg + sl] = G[F::sor + ei]; K[o_ta + sl] = G[F::sor + F::sos + ei]; K[o_ga + sl] = G[F::sor + 2 * F::sos + ei];
+                }
+            }
         }
         if (tid() == 0) {
             double* st = A.stats + (size_t)b * UPR_NSTATS;

@@ -214,6 +214,44 @@ class BatchMPC:
         check(self._lib.upr_batch_qp_slacks(self._h, ptr(out["slack"])))
         return out
 
+    def qp_slack_pairs(self):
+        """Slack pairs (sigma, tau, gam) of the softened rows of the QP the last qp_kkt() solved, each (B, N + 1, ni) in the slot
+        order of lam: 0 / 1 / 0 where a slot is not a softened row of the knot (upr_batch_qp_slack_pairs)."""
+        shape = (self.B, self.N + 1, 2 * self.nx + 2 * self.nu + (5 * self.problem.nc if self.problem.nf == 3 else 0) + self.problem.n_state_rows)
+        sig, tau, gam = np.zeros(shape), np.ones(shape), np.zeros(shape)
+        check(self._lib.upr_batch_qp_slack_pairs(self._h, ptr(sig), ptr(tau), ptr(gam)))
+        return sig, tau, gam
+
+    # -- value function of the last QP, batched on the device --------------------------------------------
+    def value_function_update(self):
+        """Linearise at the current plan, solve one QP there and run the cost-to-go kernel for every instance; statistics and
+        dispatch keys of the last advance are left as they were (upr_batch_value_function_update)."""
+        check(self._lib.upr_batch_value_function_update(self._h))
+
+    def value_function(self, t, x, inst=None):
+        """V (n,) and dV/dx (n, nx) at n points: states x (n, nx), times t (scalar or (n,)), instance of each point (default:
+        point i belongs to instance i when n == B, else instance 0)."""
+        x = cont(x).reshape(-1, self.nx)
+        n = x.shape[0]
+        t = cont(np.broadcast_to(np.asarray(t, dtype=np.float64), (n,)))
+        if inst is None:
+            inst = np.arange(n) if n == self.B else np.zeros(n)
+        inst = cont(np.broadcast_to(np.asarray(inst), (n,)), dtype=np.int32)
+        V, g = np.zeros(n), np.zeros((n, self.nx))
+        check(self._lib.upr_batch_value_function(self._h, n, iptr(inst), ptr(t), ptr(x), ptr(V), ptr(g)))
+        return V, g
+
+    def cost_to_go(self):
+        """dict(Pk (B, N + 1, nx, nx), pk (B, N + 1, nx), J (B, N + 1), X (B, N + 1, nx)) of the last value_function_update()."""
+        out = dict(Pk=np.zeros((self.B, self.N + 1, self.nx, self.nx)), pk=np.zeros((self.B, self.N + 1, self.nx)),
+                   J=np.zeros((self.B, self.N + 1)), X=np.zeros((self.B, self.N + 1, self.nx)))
+        check(self._lib.upr_batch_get_cost_to_go(self._h, ptr(out["Pk"]), ptr(out["pk"]), ptr(out["J"]), ptr(out["X"])))
+        return out
+
+    def value_function_ms(self):
+        """Device time (ms) of the last cost-to-go launch."""
+        return float(self._lib.upr_batch_value_function_ms(self._h))
+
     def device_ptrs(self):
         xs, us = C.c_void_p(), C.c_void_p()
         check(self._lib.upr_batch_device_ptrs(self._h, C.byref(xs), C.byref(us)))
