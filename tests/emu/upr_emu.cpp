@@ -15,6 +15,7 @@
 #include "../../upright_amd/csrc/upr_qp2.h"
 #include "../../upright_amd/csrc/upr_qp3.h"
 #include "../../upright_amd/csrc/upr_qp3_list.h"
+#include "../../upright_amd/csrc/upr_qp_select.h"
 
 template <int NQ, bool ORI>
 static void lin_all_o(const upr_lin_args& A);
@@ -148,38 +149,6 @@ void emu_qp(const upr_problem* P, int B, const double* xs, const double* us, con
     for (int b = 0; b < B; ++b) upr_qp_solve(ctx, A, b, L.data());
 }
 
-// third-structure kernel body (NT = 1 emulation of the <9,1,4,3,N=20> instantiation)
-long emu_qp3(const upr_problem* P, int B, const double* xs, const double* us, const double* x0, const double* lin,
-             const double* Df, double* ws, long ws_stride, double* stats) {
-    upr_qp_args A;
-    A.P = P; A.d = upr_make_dims(P); A.xs = xs; A.us = us; A.x0 = x0; A.lin = lin; A.Df = Df; A.ws = ws; A.stats = stats; A.prof = nullptr;
-    const bool softb = P->soft_state_box || P->soft_input_box || (P->soft_poly && (A.d.np > 0 || A.d.no > 0));   // upr_api.hip needs_soft
-    // the instantiations libupright_mi launches (upr_api.hip: headline, UPR_QP3_EXTRA), one thread per workgroup
-#define EMU_QP3(a, b, c, e, sf, cond) EMU_QP3N(a, b, c, e, 20, sf, false, cond)
-#define EMU_QP3D(a, b, c, e, sf, dense, cond) EMU_QP3N(a, b, c, e, 20, sf, dense, cond)
-#define EMU_QP3N(a, b, c, e, n, sf, dense, cond) if (P->nq == a && P->nb == b && P->nc == c && P->nf == e && P->N == n && (cond)) { \
-        typedef upr_qp3_cfg<a, b, c, e, n, 1, true, sf, dense> C; \
-        if (!ws) return (long)upr_qp3_ws<C>::total; \
-        A.d.ws_stride = (int)ws_stride; \
-        upr_ctx ctx; ctx.tid = 0; ctx.nt = 1; \
-        std::vector<double> L(upr_qp3_lds<C>::total + 16, std::nan("")); \
-        for (int bb = 0; bb < B; ++bb) upr_qp3_solve<C>(ctx, A, bb, L.data()); \
-        return 0; }
-    EMU_QP3(9, 1, 4, 3, false, !softb)
-    EMU_QP3(9, 1, 4, 3, true, softb)
-    EMU_QP3(9, 1, 4, 1, true, true)
-    EMU_QP3(9, 8, 32, 1, true, true)
-    EMU_QP3D(9, 3, 16, 3, false, true, !softb)
-    EMU_QP3N(6, 1, 4, 1, 20, true, false, true)
-    EMU_QP3N(6, 1, 4, 1, 10, true, false, true)
-    EMU_QP3D(9, 7, 28, 3, false, false, !softb)   // round 4: seven cups (star, friction: BIGF), two stacked dice, arm-only with friction
-    EMU_QP3D(9, 2, 8, 3, false, true, !softb)
-    EMU_QP3N(6, 1, 4, 3, 20, false, false, !softb)
-#undef EMU_QP3
-#undef EMU_QP3D
-#undef EMU_QP3N
-    return -1;
-}
 // The production QP kernel's body for EXACTLY the instantiation cfg = (nq, nb, nc, nf, N, ROWS, SOFT, DENSE) -- at NT = 1, one thread
 // per workgroup -- whichever instantiation the engine would pick for P.  The entries are the library's own list (upr_qp3_list.h:
 // UPR_QP3_PART0, UPR_QP3_EXTRA) expanded here, plus EMU_QP3_RUN_TIME: shapes that tests run through the run-time instantiation.
@@ -206,25 +175,67 @@ long emu_qp3_cfg(const int* cfg, const upr_problem* P, int B, const double* xs, 
     UPR_QP3_PART0(EMU_Y)
     UPR_QP3_EXTRA(EMU_X)
     EMU_QP3_RUN_TIME(EMU_X)
+#undef EMU_X
+    return -1;
+}
+// the per-instance workspace of the same entries at the 256 lanes the library launches them with (emu_qp3_cfg's own figure is the
+// one-lane emulation's: the parking space of the lane-owned rows is rounded up to the workgroup); -1: cfg is not an entry
+long emu_qp3_cfg_ws256(const int* cfg) {
+#define EMU_X(a, b, c, e, n, rows, sf, dense) \
+    if (cfg[0] == a && cfg[1] == b && cfg[2] == c && cfg[3] == e && cfg[4] == n && cfg[5] == (int)rows && cfg[6] == (int)sf && cfg[7] == (int)dense) \
+        return (long)upr_qp3_ws<upr_qp3_cfg<a, b, c, e, n, 256, rows, sf, dense>>::total;
+    UPR_QP3_PART0(EMU_Y)
+    UPR_QP3_EXTRA(EMU_X)
+    EMU_QP3_RUN_TIME(EMU_X)
 #undef EMU_Y
 #undef EMU_X
     return -1;
 }
 
+// third-structure kernel body for the instantiation the engine selects for P with default knobs (upr_qp_select.h, the rules
+// upr_batch_create runs), one thread per workgroup; -1: the selection is another structure, or an instantiation emu_qp3_cfg lacks
+long emu_qp3(const upr_problem* P, int B, const double* xs, const double* us, const double* x0, const double* lin,
+             const double* Df, double* ws, long ws_stride, double* stats) {
+    const upr_qp_choice s = upr_qp_plan(*P, upr_make_dims(P), upr_qp_knobs());
+    if (s.structure != UPR_QP_STRUCT_PRODUCTION) return -1;
+    return emu_qp3_cfg(s.cfg, P, B, xs, us, x0, lin, Df, ws, ws_stride, stats);
+}
+
+// The selection record of upr_qp_select.h for P under the knobs k, as upr_batch_create resolves it (a run-time instantiation
+// reports the workspace of its 256-lane form: EMU_QP3_RUN_TIME).  out[0..23] = structure, source, the tuple [8], nt, ws_doubles,
+// ws_stride, exported, stride, o_pi, o_nu, o_yN, o_lam, o_t, o_sig, o_tau, o_gam, fb_fused; name[128]
+void emu_qp_select(const upr_problem* P, const upr_qp_knobs* k, int* out, char* name) {
+    const upr_dims d = upr_make_dims(P);
+    upr_qp_choice s = upr_qp_plan(*P, d, *k);
+    int run_time_ws = 0;
+#define EMU_X(a, b, c, e, n, rows, sf, dense) { const int t[8] = {a, b, c, e, n, rows, sf, dense}; \
+        if (std::equal(t, t + 8, s.cfg)) run_time_ws = upr_qp3_ws<upr_qp3_cfg<a, b, c, e, n, 256, rows, sf, dense>>::total; }
+    EMU_QP3_RUN_TIME(EMU_X)
+#undef EMU_X
+    upr_qp_resolve(s, *P, d, run_time_ws, upr_qp_no_visit());
+    const int v[23] = {s.structure, s.source, s.cfg[0], s.cfg[1], s.cfg[2], s.cfg[3], s.cfg[4], s.cfg[5], s.cfg[6], s.cfg[7], s.nt, s.ws_doubles,
+                       s.ws_stride, s.exported, s.stride, s.o_pi, s.o_nu, s.o_yN, s.o_lam, s.o_t, s.o_sig, s.o_tau, s.o_gam};
+    std::copy(v, v + 23, out);
+    out[23] = s.fb_fused;
+    std::copy(s.name, s.name + sizeof(s.name), name);
+}
+
 long emu_qp3_lds_doubles() { return (long)upr_qp3_lds<upr_qp3_cfg<9, 1, 4, 3, 20, 256>>::total; }
 
-// production kernel body; returns the per-instance workspace size it needs (doubles) when ws == NULL
+// second-structure kernel body, the shapes libupright_mi instantiates it for (a list of its own: the selection test holds
+// upr_qp_select.h's against it); ws == NULL: the per-instance workspace (doubles) it needs; -1: not one of its shapes
 long emu_qp2(const upr_problem* P, int B, const double* xs, const double* us, const double* x0, const double* lin,
              const double* Df, double* ws, long ws_stride, double* stats) {
     upr_qp_args A;
     A.P = P; A.d = upr_make_dims(P); A.xs = xs; A.us = us; A.x0 = x0; A.lin = lin; A.Df = Df; A.ws = ws; A.stats = stats; A.prof = nullptr;
-    if (P->nq == 9 && P->nb == 1 && P->nc == 4 && P->nf == 3) {
-        typedef upr_qp2_dims<9, 1, 4, 3> D;
-        if (!ws) return (long)upr_qp2_ws_doubles<D>(A.d.N, A.d.neN);
-        A.d.ws_stride = (int)ws_stride;
-        qp2_all<D>(A, B);
-        return 0;
-    }
+#define EMU_QP2(a, b, c, e) if (P->nq == a && P->nb == b && P->nc == c && P->nf == e) { \
+        typedef upr_qp2_dims<a, b, c, e> D; \
+        if (!ws) return (long)upr_qp2_ws_doubles<D>(A.d.N, A.d.neN); \
+        A.d.ws_stride = (int)ws_stride; \
+        qp2_all<D>(A, B); \
+        return 0; }
+    EMU_QP2(9, 1, 4, 3) EMU_QP2(9, 1, 4, 1) EMU_QP2(6, 1, 4, 1) EMU_QP2(6, 1, 4, 3) EMU_QP2(9, 2, 8, 3)
+#undef EMU_QP2
     return -1;
 }
 

@@ -9,6 +9,7 @@
 #include "../../upright_amd/csrc/upr_kin.h"
 #include "../../upright_amd/csrc/upr_qp.h"
 #include "../../upright_amd/csrc/upr_qp3.h"
+#include "../../upright_amd/csrc/upr_qp_select.h"
 #include "../../upright_amd/csrc/upr_value.h"
 
 extern "C" {
@@ -19,11 +20,9 @@ long emu_vf_kkt_doubles(const upr_problem* P) { return (long)upr_kkt_doubles(upr
 // softened inequality rows), ni: kernel 3 in the export buffer of the production kernel, kernel 1 in the generic kernel's workspace
 void emu_vf_offsets(const upr_problem* P, int kernel, int* out) {
     const upr_dims d = upr_make_dims(P);
-    const int nsl = (d.N + 1) * d.ni_stage;
-    if (kernel == 3) { out[0] = 0; out[1] = (d.N + 1) * d.nx; out[2] = out[1] + d.N * d.ne + d.neN; out[3] = out[2] + nsl; out[4] = out[3] + nsl; out[5] = out[4] + nsl; out[6] = out[5] + nsl; }
-    else { out[0] = d.ws_pi; out[1] = d.ws_nu; out[2] = d.ws_lam; out[3] = d.ws_t; out[4] = d.ws_sig; out[5] = d.ws_tau; out[6] = d.ws_gam; }
-    const bool pairs = d.soft && (kernel != 3 || P->soft_state_box || P->soft_input_box || (P->soft_poly && (d.np > 0 || d.no > 0)));   // (upr_api.hip: vf_has_pairs)
-    if (!pairs) out[4] = out[5] = out[6] = -1;
+    upr_qp_choice s;   // (the selection record's offsets for that structure: upr_qp_select.h)
+    if (kernel == 3) upr_qp_point_exported(s, *P, d); else upr_qp_fill_generic(s, d);
+    out[0] = s.o_pi; out[1] = s.o_nu; out[2] = s.o_lam; out[3] = s.o_t; out[4] = s.o_sig; out[5] = s.o_tau; out[6] = s.o_gam;
     out[7] = d.ni_stage;
 }
 
@@ -34,7 +33,7 @@ long emu_vf_qp3(const upr_problem* P, int B, const double* xs, const double* us,
     upr_qp_args A;
     A.P = P; A.d = upr_make_dims(P); A.xs = xs; A.us = us; A.x0 = x0; A.lin = lin; A.Df = Df; A.ws = ws; A.stats = stats; A.prof = nullptr;
     A.kkt = kkt; A.kkt_stride = (int)kkt_stride;
-    const bool softb = P->soft_state_box || P->soft_input_box || (P->soft_poly && (A.d.np > 0 || A.d.no > 0));
+    const bool softb = upr_qp_needs_soft(*P, A.d);
 #define EMU_QP3(a, b, c, e, n, sf, cond) if (P->nq == a && P->nb == b && P->nc == c && P->nf == e && P->N == n && (cond)) { \
         typedef upr_qp3_cfg<a, b, c, e, n, 1, true, sf, false> C; \
         if (!ws) return (long)upr_qp3_ws<C>::total; \

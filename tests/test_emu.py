@@ -656,3 +656,131 @@ def test_every_qp_instantiation_has_a_screen_case():
     arr = json.load(open(Path(__file__).resolve().parent / "golden" / "arrangements.json"))
     forms = {GOLDEN_LS[n][1] if n in GOLDEN_LS else ls_case(arr, n)["form"] for n in DEVICE_CASES}
     assert forms == {EXACT, EXACT_ROWS, SMALL, LARGE}, forms
+
+
+class _Knobs(C.Structure):
+    """upr_qp_knobs of upr_qp_select.h: the environment knobs of the selection as upr_batch_create reads them."""
+    _fields_ = [("qp_kernel", C.c_int), ("qp_generic", C.c_bool), ("qp3_jit", C.c_int), ("qp_nt_set", C.c_bool), ("qp_nt", C.c_int),
+                ("generic_nt_set", C.c_bool), ("generic_nt", C.c_int), ("jit_nt", C.c_int), ("fb_fused", C.c_bool)]
+
+
+def _knobs(**kw):
+    k = dict(qp_kernel=3, qp_generic=False, qp3_jit=1, qp_nt_set=False, qp_nt=0, generic_nt_set=False, generic_nt=0, jit_nt=256, fb_fused=True)
+    k.update(kw)
+    return _Knobs(**k)
+
+
+def _select(E, P, knobs):
+    """The selection record for P under the knobs (emu_qp_select), as a dict."""
+    out = (C.c_int * 24)()
+    name = C.create_string_buffer(128)
+    cp = _capi.problem_to_c(P)
+    E.emu_qp_select(C.byref(cp), C.byref(knobs), out, name)
+    v = list(out)
+    keys = ("nt", "ws_doubles", "ws_stride", "exported", "stride", "o_pi", "o_nu", "o_yN", "o_lam", "o_t", "o_sig", "o_tau", "o_gam", "fb_fused")
+    rec = dict(structure=v[0], source=v[1], cfg=tuple(v[2:7]) + tuple(bool(w) for w in v[7:10]), name=name.value.decode())
+    rec.update(zip(keys, v[10:]))
+    return rec
+
+
+class _NoDevice:
+    """Stands in for BatchMPC while a controller manager builds its Problem (the golden configs of the screen's table): no handle."""
+
+    def __init__(self, problem, B=1, **kw):
+        self.problem = problem
+
+    def close(self):
+        pass
+
+    def set_projectile_flag(self, flag):
+        pass
+
+
+def test_qp_selection_record(monkeypatch):
+    """The selection of upr_qp_select.h -- the rules upr_batch_create resolves a handle's QP kernel with -- on the host: every case of
+    the GPU screen's table resolves to the instantiation it is filed under (listed or run-time as the table says), the override
+    knobs give the structure and the name of the rules as they were before the record existed (names written out), and the
+    workspace stride and the offsets of the primal-dual point equal what entry points that do not go through the record (emu_dims,
+    emu_qp2, emu_qp3_cfg / emu_qp3_cfg_ws256) and the closed form of the export buffer (upr_kkt_doubles) give."""
+    import sys
+    sys.path.insert(0, str(Path(__file__).resolve().parent))
+    import test_gpu_qp_screen as S
+    from upright_amd import control_bindings
+
+    monkeypatch.setattr(control_bindings, "BatchMPC", _NoDevice)   # (the builders keep the manager's Problem and close its handle)
+    E = C.CDLL(str(EMU))
+    V = C.CDLL(str(EMU.parent / "libupr_vf_emu.so"))
+    for f in (E.emu_qp2, E.emu_qp3_cfg, E.emu_qp3_cfg_ws256, V.emu_vf_kkt_doubles):
+        f.restype = C.c_long
+    GENERIC, SECOND, PRODUCTION = 1, 2, 3
+    HEADLINE, LISTED, RUN_TIME = 0, 1, 2
+
+    def check_sizes(P, r):
+        cp = _capi.problem_to_c(P)
+        d = (C.c_int * 16)()
+        E.emu_dims(C.byref(cp), d)
+        nx, ne, ws_generic = d[0], d[2], d[5]
+        ko = (C.c_int * 8)()
+        E.emu_kkt_offsets(C.byref(cp), ko)
+        ni, neN = ko[4], ko[5]
+        # the stride: the generic layout's, the second structure's where its entry has the shape, the production selection's -- at the
+        # 256 lanes the library launches (emu_qp3_cfg's own figure is the one-lane emulation's, smaller by the rounding of the
+        # lane-owned rows' parking space to the workgroup: 34 224 against 38 704 doubles for the headline with slacks on its boxes)
+        need = [ws_generic]
+        n2 = E.emu_qp2(C.byref(cp), 1, None, None, None, None, None, None, C.c_long(0), None)
+        if n2 > 0:
+            need.append(n2)
+        if r["structure"] == PRODUCTION:
+            c = (C.c_int * 8)(*[int(v) for v in r["cfg"]])
+            n1 = E.emu_qp3_cfg(c, None, 1, None, None, None, None, None, None, C.c_long(0), None)
+            n3 = E.emu_qp3_cfg_ws256(c)
+            assert 0 < n1 <= n3 and n3 == r["ws_doubles"], (r, n1, n3)
+            need.append(n3)
+        print("   ws_stride %d; generic / second / production: %s" % (r["ws_stride"], need))
+        assert r["ws_stride"] == max(need), (r, need)
+        # the primal-dual point
+        offs = [r[k] for k in ("o_pi", "o_nu", "o_yN", "o_lam")]
+        nsl = (P.N + 1) * ni
+        if r["structure"] == GENERIC:
+            assert not r["exported"] and r["stride"] == r["ws_stride"] and offs == list(ko[:4]), (r, list(ko))
+        elif r["structure"] == PRODUCTION:
+            kd = V.emu_vf_kkt_doubles(C.byref(cp))
+            o_nu = (P.N + 1) * nx
+            assert r["exported"] and r["stride"] == kd and offs == [0, o_nu, o_nu + P.N * ne, o_nu + P.N * ne + neN], (r, kd)
+            assert r["o_t"] == r["o_lam"] + nsl
+            if r["o_sig"] >= 0:
+                assert (r["o_sig"], r["o_tau"], r["o_gam"]) == (r["o_t"] + nsl, r["o_t"] + 2 * nsl, r["o_t"] + 3 * nsl) and r["o_gam"] + nsl == kd, (r, kd)
+            else:
+                assert r["o_tau"] == r["o_gam"] == -1 and r["o_t"] + nsl in (kd, kd - 3 * nsl), (r, kd)
+        else:
+            assert not r["exported"] and r["stride"] == r["ws_stride"] and all(0 <= o < r["ws_doubles"] for o in offs + [r["o_t"]]), r
+            assert r["o_sig"] == r["o_tau"] == r["o_gam"] == -1
+
+    # every case of the screen's table, default knobs: the tuple it is filed under, listed unless the table says run-time
+    for cfg, (builder, kw, jit) in S.CASES.items():
+        kw = {k: v for k, v in kw.items() if k != "iters"}
+        P = builder(**kw)["P"]
+        r = _select(E, P, _knobs())
+        print("default knobs %s: %s" % (S._ids(cfg), r))
+        assert r["structure"] == PRODUCTION and r["cfg"] == cfg, (cfg, r)
+        assert (r["source"] == RUN_TIME) == (jit is not None), (cfg, r)
+        if jit is None:
+            assert r["source"] == (HEADLINE if cfg[:5] == (9, 1, 4, 3, 20) and not cfg[6] else LISTED), (cfg, r)
+        ran, is_jit = S.parse_qp_kernel(r["name"])
+        assert ran == cfg and is_jit == (jit is not None) and r["nt"] == 256 and r["fb_fused"], r
+        check_sizes(P, r)
+
+    # the override knobs: the second structure only for a listed shape without rows or slacks, otherwise the generic kernel
+    headline, soft_boxes, box_arch = S._headline()["P"], S._soft_boxes()["P"], S._box_arch()["P"]
+    qp2, gen = "upr_qp2_kernel<upr_qp2_dims<9, 1, 4, 3>, 128>", "upr_qp_kernel<256>"
+    expected = {
+        "UPR_QP_KERNEL=2": (dict(qp_kernel=2), [(SECOND, qp2), (GENERIC, gen), (GENERIC, gen)]),
+        "UPR_QP_KERNEL=1": (dict(qp_kernel=1), [(GENERIC, gen), (GENERIC, gen), (GENERIC, gen)]),
+        "UPR_QP_GENERIC=1": (dict(qp_generic=True), [(GENERIC, gen), (GENERIC, gen), (GENERIC, gen)]),
+    }
+    for knob, (kw, exp) in expected.items():
+        for P, (structure, name) in zip((headline, soft_boxes, box_arch), exp):
+            r = _select(E, P, _knobs(**kw))
+            print("%s: %s" % (knob, r))
+            assert (r["structure"], r["name"]) == (structure, name) and not r["fb_fused"], (knob, r)
+            check_sizes(P, r)

@@ -30,6 +30,7 @@
 #include "upr_qp3.h"
 #include "upr_qp3_list.h"
 #include "upr_qp3_launch.h"
+#include "upr_qp_select.h"
 #include "upr_value.h"
 
 namespace {
@@ -243,7 +244,14 @@ struct upr_jit_kernel {
     size_t lds = 0, ws = 0;
     int nt = 256;       // lanes per workgroup (UPR_JIT_NT: 128 | 256 | 512, experiments)
     std::string cfg;    // the template arguments, as rocprofv3 prints them
-    int fbo[7] = {0, 0, 0, 0, 0, 0, 0};   // where this instantiation leaves K, Lf^-1, Ls^-1 (fb_source): far + Ks, nq nx, far + lfi, NLF, far + lsi, NLS, SB
+    upr_fb_src fb{};    // where this instantiation leaves K, Lf^-1, Ls^-1, as its own info kernel reported them
+};
+
+// the QP kernel of a handle, resolved once at upr_batch_create: the record of upr_qp_select.h and what only this file knows
+struct upr_qp_sel : upr_qp_choice {
+    int (*launch)(struct upr_batch*, const upr_qp_args&) = nullptr;
+    upr_jit_kernel* jit = nullptr;   // production kernel from a run-time instantiation: its module function, nt and lds
+    upr_fb_src fb{};                 // where the kernel leaves its per-knot factors (kind 0 = no source: the feedback launch is refused)
 };
 
 struct upr_batch {
@@ -282,11 +290,7 @@ struct upr_batch {
     bool guess_set = false;
     int sqp_iters_next = 0;   // > 0: SQP iterations of the next advance only (init_sqp_iteration of the first solve)
     double last_ms = 0.0;
-    int qp_nt = 0;
-    bool use_qp2 = false;
-    int use_qp3 = 0;   // 0: no; 1: headline instantiations; 2: one of UPR_QP3_EXTRA (qp3_variant); 3: instantiated at run time (jit)
-    struct upr_jit_kernel* jit = nullptr;
-    bool fb_fused = false;   // the selected QP kernel writes the feedback gains itself (upr_qp_args::fb)
+    upr_qp_sel qp;   // the QP kernel instantiation this handle launches
     bool use_mfma = true;
     bool lin2 = true;   // shapes without collision rows / orientation cost: upr_linearize2_kernel (UPR_LIN2=0 at create: upr_linearize_kernel)
     int timing = 0;   // 0: no events; 1: around every kernel of an advance; 2: around the QP kernel only; 3: around every FOURTH QP launch
@@ -303,7 +307,6 @@ struct upr_batch {
     int vf_state = 0;        // 0: no update yet; 1: current; 2: stale (the plan or the observation changed since)
     double vf_ms = 0.0;      // device time of the last cost-to-go launch
     hipEvent_t vf_ev[2] = {nullptr, nullptr};
-    std::string qp_name;   // the QP kernel instantiation this handle launches
     std::string ls_name;   // the line-search kernel instantiation of the handle's last line-search launch (upr_batch_ls_kernel_name)
     int ls_form[5] = {0, 0, 0, 0, -1};   // (NFM, NBM, EXACT, OBS, STAGE) of that launch; STAGE -1: no line search launched yet
     std::vector<hipEvent_t> ev_pool, ev_free;   // events in use (pairs, in launch order) / harvested ones waiting for reuse
@@ -407,9 +410,9 @@ int launch_linearize(upr_batch* h, const upr_lin_args& A) {
     return 0;
 }
 
-// generic (runtime-dimension) QP kernel.  Its LDS footprint (one knot's matrices) allows one or two workgroups per CU for
-// the multi-body shapes, so the workgroup size IS the occupancy: 64 lanes left 3 of 4 SIMDs of a CU idle.  NT is chosen by
-// the size of the per-knot phases (ne x nx, nx x nx, ne x ne items); UPR_QP_GENERIC_NT overrides it.
+typedef int (*upr_qp_launcher)(upr_batch*, const upr_qp_args&);
+
+// generic (runtime-dimension) QP kernel, at the workgroup size upr_qp_generic_nt chose
 template <int NT>
 int launch_qp_generic_nt(upr_batch* h, const upr_qp_args& A) {
     const upr_qp_lds lay = upr_qp_lds_layout(A.d, NT);
@@ -420,20 +423,15 @@ int launch_qp_generic_nt(upr_batch* h, const upr_qp_args& A) {
     UPR_HIP(hipGetLastError());
     return 0;
 }
-int generic_nt(const upr_batch* h) {
-    if (const char* e = getenv("UPR_QP_GENERIC_NT")) return atoi(e);
-    const upr_dims& d = h->d;
-    const int big = d.ne * d.nx > d.nx * d.nx ? d.ne * d.nx : d.nx * d.nx;
-    return big >= 1024 ? 512 : (big >= 512 ? 256 : 64);
-}
-int launch_qp_generic(upr_batch* h, const upr_qp_args& A) {
-    switch (generic_nt(h)) {
-        case 64: return launch_qp_generic_nt<64>(h, A);
-        case 128: return launch_qp_generic_nt<128>(h, A);
-        case 256: return launch_qp_generic_nt<256>(h, A);
-        case 512: return launch_qp_generic_nt<512>(h, A);
-        case 1024: return launch_qp_generic_nt<1024>(h, A);
-        default: return fail("UPR_QP_GENERIC_NT must be 64, 128, 256, 512 or 1024");
+int launch_qp_generic_bad_nt(upr_batch*, const upr_qp_args&) { return fail("UPR_QP_GENERIC_NT must be 64, 128, 256, 512 or 1024"); }
+upr_qp_launcher qp_generic_launcher(int nt) {
+    switch (nt) {
+        case 64: return launch_qp_generic_nt<64>;
+        case 128: return launch_qp_generic_nt<128>;
+        case 256: return launch_qp_generic_nt<256>;
+        case 512: return launch_qp_generic_nt<512>;
+        case 1024: return launch_qp_generic_nt<1024>;
+        default: return launch_qp_generic_bad_nt;
     }
 }
 
@@ -446,40 +444,20 @@ int launch_qp2_nt(upr_batch* h, const upr_qp_args& A) {
     UPR_HIP(hipGetLastError());
     return 0;
 }
+int launch_qp2_bad_nt(upr_batch*, const upr_qp_args&) { return fail("UPR_QP_NT must be 64, 128 or 256"); }
 template <class D>
-int launch_qp2(upr_batch* h, const upr_qp_args& A) {
-    switch (h->qp_nt) {
-        case 64: return launch_qp2_nt<D, 64>(h, A);
+upr_qp_launcher qp2_launcher(int nt) {
+    switch (nt) {
+        case 64: return launch_qp2_nt<D, 64>;
         case 512:
-        case 128: return launch_qp2_nt<D, 128>(h, A);
-        case 256: return launch_qp2_nt<D, 256>(h, A);
-        default: return fail("UPR_QP_NT must be 64, 128 or 256");
+        case 128: return launch_qp2_nt<D, 128>;
+        case 256: return launch_qp2_nt<D, 256>;
+        default: return launch_qp2_bad_nt;
     }
 }
 
-// shapes the production kernel is instantiated for: (nq, nb, nc, nf)
-// -DUPR_HEADLINE_ONLY: experiment builds of the headline kernel (a tenth of the compile time); never the production library
-#ifdef UPR_HEADLINE_ONLY
-#define UPR_QP2_SHAPES(X) X(9, 1, 4, 3)
-#else
-#define UPR_QP2_SHAPES(X) X(9, 1, 4, 3) X(9, 1, 4, 1) X(6, 1, 4, 1) X(6, 1, 4, 3) X(9, 2, 8, 3)
-#endif
-
-bool qp2_has_shape(const upr_problem& P) {
-#define X(a, b, c, e) if (P.nq == a && P.nb == b && P.nc == c && P.nf == e) return true;
-    UPR_QP2_SHAPES(X)
-#undef X
-    return false;
-}
-size_t qp2_ws_doubles(const upr_problem& P, const upr_dims& d) {
-#define X(a, b, c, e) if (P.nq == a && P.nb == b && P.nc == c && P.nf == e) return upr_qp2_ws_doubles<upr_qp2_dims<a, b, c, e>>(d.N, d.neN);
-    UPR_QP2_SHAPES(X)
-#undef X
-    return 0;
-}
-
-// third-structure ("production") kernel.  The headline shape (nq 9, nb 1, nc 4, nf 3, N 20) in three workgroup sizes, with
-// and without state-polytopic rows; further (shape, SOFT) instantiations at 256 lanes for the configurations the
+// third-structure ("production") kernel.  The headline shape (nq 9, nb 1, nc 4, nf 3, N 20) at 256 lanes, with and without
+// state-polytopic rows; further (shape, SOFT) instantiations at 256 lanes for the configurations the
 // reference ships with HPIPM slacks: thing_demo (one body, frictionless) and the upright_robust 8-corner arrangement.
 // (the kernels themselves are instantiated in upr_qp3_inst.hip, one translation unit per part of upr_qp3_list.h, compiled side
 // by side; this file only declares their launchers -- -DUPR_MONOLITHIC instantiates them here instead: experiment builds)
@@ -490,43 +468,47 @@ int launch_qp3_cfg(upr_batch* h, const upr_qp_args& A) {
     if (rc != 0) return fail(std::string("upr_qp3_kernel launch: ") + hipGetErrorString((hipError_t)rc));
     return 0;
 }
-bool qp3_is_headline(const upr_problem& P) { return P.nq == 9 && P.nb == 1 && P.nc == 4 && P.nf == 3 && P.N == 20; }
-bool soft_boxes(const upr_problem& P) { return P.soft_state_box || P.soft_input_box; }
-// does the problem need a SOFT instantiation?  Slacks on its boxes, or slacks.poly_ineq with friction / state-polytopic rows
-bool needs_soft(const upr_problem& P, const upr_dims& d) { return soft_boxes(P) || (P.soft_poly && (d.np > 0 || d.no > 0)); }
-// does instantiation (a, b, c, e, horizon n, rows, sf, dense) of UPR_QP3_EXTRA take this problem?  (The first match in list order is the one
-// every site below uses: a SOFT problem without state-polytopic rows takes the instantiation without them.)
-bool qp3_match(const upr_problem& P, const upr_dims& d, int a, int b, int c, int e, int n, bool rows, bool sf, bool dense) {
-    bool star = true;                                         // no two bodies share a contact point
-    for (int i = 0; i < P.nc; ++i) if (P.contact_body1[i] >= 0) star = false;
-    return P.nq == a && P.nb == b && P.nc == c && P.nf == e && P.N == n && (rows || d.no == 0) && (sf || !needs_soft(P, d)) && (dense || star);
+int launch_qp3_bad_nt(upr_batch*, const upr_qp_args&) {
+    return fail("the production QP kernel ships at 256 lanes (UPR_QP_NT = 128 | 512 were A/B instantiations of rounds 1 - 5; UPR_QP3_JIT=2 UPR_JIT_NT=... instantiates one at run time)");
 }
-// can the production kernel take this problem, and in which instantiation?  0: no; 1: headline (hard boxes); 2: one of
-// UPR_QP3_EXTRA
-int qp3_variant(const upr_problem& P, const upr_dims& d) {
-    if (d.no > UPR_QP3_NOMAX) return 0;
-    // (a hard equality the contact forces cannot span -- frictionless one-body arrangements: nf nc < 6 nb -- gets the proximal
-    // treatment of upr_qp.h inside the kernel; multi-body shapes of that kind need soft_eq)
-    if (d.nfc < d.ne && !P.soft_eq && P.nb > 1) return 0;
-    if (qp3_is_headline(P) && !needs_soft(P, d)) return 1;
-#define X(a, b, c, e, n, rows, sf, dense) if (qp3_match(P, d, a, b, c, e, n, rows, sf, dense)) return 2;
-    UPR_QP3_EXTRA(X)
-#undef X
+int launch_qp3_run_time(upr_batch* h, const upr_qp_args& A) {
+    const upr_jit_kernel* k = h->qp.jit;
+    upr_qp_args Ac = A;
+    void* args[] = {&Ac};
+    UPR_HIP(hipModuleLaunchKernel(k->fn, (unsigned)h->B, 1, 1, (unsigned)k->nt, 1, 1, (unsigned)k->lds, h->stream, args, nullptr));
     return 0;
 }
-template <int NT, bool ROWS>
-int launch_qp3_rows(upr_batch* h, const upr_qp_args& A) { return launch_qp3_cfg<upr_qp3_cfg<9, 1, 4, 3, 20, NT, ROWS>>(h, A); }
-// problems without state-polytopic rows run the instantiation that has none compiled in (upr_qp3.h, upr_qp3_cfg)
-template <int NT>
-int launch_qp3(upr_batch* h, const upr_qp_args& A) {
-    return (h->d.no > 0) ? launch_qp3_rows<NT, true>(h, A) : launch_qp3_rows<NT, false>(h, A);
-}
-size_t qp3_ws_doubles(const upr_problem& P, const upr_dims& d, int variant) {
-    if (variant == 1) return upr_qp3_ws<upr_qp3_cfg<9, 1, 4, 3, 20, 256>>::total;
-#define X(a, b, c, e, n, rows, sf, dense) if (qp3_match(P, d, a, b, c, e, n, rows, sf, dense)) return upr_qp3_ws<upr_qp3_cfg<a, b, c, e, n, 256, rows, sf, dense>>::total;
-    UPR_QP3_EXTRA(X)
-#undef X
-    return 0;
+
+// what upr_qp_resolve's visitor adds for one of the library's own kernels: its launcher and the place of its per-knot factors
+struct qp_sel_own {
+    upr_qp_sel& s;
+    const upr_dims& d;
+    template <int a, int b, int c, int e, int n, int nt, bool rows, bool sf, bool dense>
+    void operator()(upr_qp3_cfg<a, b, c, e, n, nt, rows, sf, dense>) const {
+        typedef upr_qp3_cfg<a, b, c, e, n, nt, rows, sf, dense> C; typedef upr_qp3_ws<C> W; typedef upr_qp3_far<C> F;
+        s.launch = (s.nt == nt) ? launch_qp3_cfg<C> : launch_qp3_bad_nt;   // (UPR_QP_NT on the headline)
+        // (these offsets lie in front of everything that depends on the workgroup size or on ROWS / SOFT)
+        s.fb.kind = 3; s.fb.k_base = W::far + F::Ks; s.fb.k_stride = C::NQ * C::NX; s.fb.lji_base = 0; s.fb.lji_stride = 0;
+        s.fb.lfi_base = W::far + F::lfi; s.fb.lfi_stride = C::NLF; s.fb.lsi_base = W::far + F::lsi; s.fb.lsi_stride = C::NLS; s.fb.lsi_sb = C::SB;
+    }
+    template <int a, int b, int c, int e>
+    void operator()(upr_qp2_dims<a, b, c, e>) const {
+        typedef upr_qp2_dims<a, b, c, e> D;
+        const upr_qp2_ws<D> w(d.N, d.neN);
+        s.launch = qp2_launcher<D>(s.nt);
+        s.fb.kind = 2; s.fb.k_base = w.store + D::SS_V; s.fb.k_stride = D::SS_STRIDE; s.fb.lji_base = w.store + D::SS_LJI; s.fb.lji_stride = D::SS_STRIDE;
+        s.fb.lfi_base = w.pre + D::PR_LFI; s.fb.lfi_stride = D::PR_STRIDE; s.fb.lsi_base = w.pre + D::PR_LSI; s.fb.lsi_stride = D::PR_STRIDE; s.fb.lsi_sb = d.ne;
+    }
+};
+// fills the plan in s (with s.jit where it is a run-time instantiation): sizes, offsets, name, launcher, factors
+void qp_resolve(upr_qp_sel& s, const upr_problem& P, const upr_dims& d) {
+    upr_qp_resolve(s, P, d, s.jit ? (int)s.jit->ws : 0, qp_sel_own{s, d});
+    if (s.jit) { s.launch = launch_qp3_run_time; s.fb = s.jit->fb; }
+    else if (s.structure == UPR_QP_STRUCT_GENERIC) {
+        s.launch = qp_generic_launcher(s.nt);
+        s.fb.kind = 1; s.fb.k_base = d.ws_store + d.ss_kx; s.fb.k_stride = d.ss_stride; s.fb.lji_base = d.ws_store + d.ss_hjj; s.fb.lji_stride = d.ss_stride;
+        s.fb.lfi_base = d.ws_store + d.ss_hff; s.fb.lfi_stride = d.ss_stride; s.fb.lsi_base = d.ws_store + d.ss_sinv; s.fb.lsi_stride = d.ss_stride; s.fb.lsi_sb = d.ne;
+    }
 }
 
 // ---- run-time instantiation of the production kernel (round 4) ---------------------------------------------------------------
@@ -559,28 +541,11 @@ bool jit_read(const std::string& path, std::string* out) {
     std::stringstream ss; ss << f.rdbuf(); *out = ss.str();
     return true;
 }
-// can the production structure take this problem at all?  (what upr_qp3.h asserts or assumes; the LDS is checked after the compile)
-bool jit_capable(const upr_problem& P, const upr_dims& d) {
-    if (P.nq != 6 && P.nq != 9) return false;
-    // (horizons beyond 64 knots: the far-array form of the kernel, upr_qp3_cfg::KFAR -- star arrangements without friction and rows)
-    if (d.no > UPR_QP3_NOMAX || P.N < 2 || P.N > 128) return false;
-    if (P.N > 64) { for (int i = 0; i < P.nc; ++i) if (P.contact_body1[i] >= 0) return false; if (P.nb < 2 || P.nf != 1 || d.no != 0) return false; }
-    if (d.nfc < d.ne && !P.soft_eq && P.nb > 1) return false;
-    return true;
-}
-bool jit_wanted(int B) {
-    (void)B;
-    if (const char* e = getenv("UPR_QP3_JIT")) return atoi(e) != 0;
-    return true;
-}
-int jit_get(const upr_problem& P, const upr_dims& d, upr_jit_kernel** out) {
-    bool star = true;
-    for (int i = 0; i < P.nc; ++i) if (P.contact_body1[i] >= 0) star = false;
-    const bool rows = d.no > 0, soft = needs_soft(P, d), dense = !star;
+// the instantiation (tuple; nt lanes: UPR_JIT_NT) that upr_qp_plan asked for
+int jit_get(const int* tuple, int nt, upr_jit_kernel** out) {
     char cfg[128];
-    int nt = 256;
-    if (const char* e = getenv("UPR_JIT_NT")) { nt = atoi(e); if (nt != 128 && nt != 256 && nt != 512) return fail("UPR_JIT_NT must be 128, 256 or 512"); }
-    snprintf(cfg, sizeof(cfg), "%d, %d, %d, %d, %d, %d, %s, %s, %s", P.nq, P.nb, P.nc, P.nf, P.N, nt, rows ? "true" : "false", soft ? "true" : "false", dense ? "true" : "false");
+    if (nt != 128 && nt != 256 && nt != 512) return fail("UPR_JIT_NT must be 128, 256 or 512");
+    upr_qp3_cfg_text(tuple, nt, cfg, sizeof(cfg));
     int dev = 0;
     UPR_HIP(hipGetDevice(&dev));
     const std::string key = std::string(cfg) + " @" + std::to_string(dev);
@@ -691,7 +656,7 @@ int jit_get(const upr_problem& P, const upr_dims& d, upr_jit_kernel** out) {
     int hi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     UPR_HIP(hipMemcpy(hi, dp, sizeof(hi), hipMemcpyDeviceToHost));
     k.lds = (size_t)hi[0] * sizeof(double); k.ws = (size_t)hi[1];
-    for (int i = 0; i < 7; ++i) k.fbo[i] = hi[2 + i];
+    k.fb.kind = 3; k.fb.k_base = hi[2]; k.fb.k_stride = hi[3]; k.fb.lfi_base = hi[4]; k.fb.lfi_stride = hi[5]; k.fb.lsi_base = hi[6]; k.fb.lsi_stride = hi[7]; k.fb.lsi_sb = hi[8];
     if (k.lds > 160 * 1024) { (void)hipModuleUnload(k.mod); return fail("run-time instantiation: the working set of upr_qp3_cfg<" + std::string(cfg) + "> exceeds 160 KiB of LDS"); }
     if (k.lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
     auto ins = g_jit.emplace(key, k);
@@ -699,31 +664,7 @@ int jit_get(const upr_problem& P, const upr_dims& d, upr_jit_kernel** out) {
     return 0;
 }
 
-int launch_qp(upr_batch* h, const upr_qp_args& A) {
-    if (h->use_qp3 == 3) {
-        upr_qp_args Ac = A;
-        void* args[] = {&Ac};
-        UPR_HIP(hipModuleLaunchKernel(h->jit->fn, (unsigned)h->B, 1, 1, (unsigned)h->jit->nt, 1, 1, (unsigned)h->jit->lds, h->stream, args, nullptr));
-        return 0;
-    }
-    if (h->use_qp3 == 1) {
-        switch (h->qp_nt) {
-            case 256: return launch_qp3<256>(h, A);
-            default: return fail("the production QP kernel ships at 256 lanes (UPR_QP_NT = 128 | 512 were A/B instantiations of rounds 1 - 5; UPR_QP3_JIT=2 UPR_JIT_NT=... instantiates one at run time)");
-        }
-    }
-    if (h->use_qp3 == 2) {
-#define X(a, b, c, e, n, rows, sf, dense) if (qp3_match(h->P, h->d, a, b, c, e, n, rows, sf, dense)) return launch_qp3_cfg<upr_qp3_cfg<a, b, c, e, n, 256, rows, sf, dense>>(h, A);
-        UPR_QP3_EXTRA(X)
-#undef X
-    }
-    if (h->use_qp2) {
-#define X(a, b, c, e) if (h->P.nq == a && h->P.nb == b && h->P.nc == c && h->P.nf == e) return launch_qp2<upr_qp2_dims<a, b, c, e>>(h, A);
-        UPR_QP2_SHAPES(X)
-#undef X
-    }
-    return launch_qp_generic(h, A);
-}
+int launch_qp(upr_batch* h, const upr_qp_args& A) { return h->qp.launch(h, A); }
 
 template <int NQ>
 int launch_linesearch(upr_batch* h, const upr_ls_args& A0) {
@@ -801,40 +742,6 @@ struct KernelTimer {
     void stop() { if (on) (void)hipEventRecord(h->ev_pool[idx + 1], h->stream); }
 };
 
-// where the QP kernel selected for this handle keeps its per-knot factors
-upr_fb_src fb_source(const upr_batch* h) {
-    upr_fb_src s{};   // (kind 0 = no source: the caller refuses to launch)
-    const upr_dims& d = h->d;
-    if (h->use_qp3) {
-        auto fill = [&](auto cfg) {
-            typedef decltype(cfg) C; typedef upr_qp3_ws<C> W; typedef upr_qp3_far<C> F;
-            s.kind = 3; s.k_base = W::far + F::Ks; s.k_stride = C::NQ * C::NX; s.lji_base = 0; s.lji_stride = 0;
-            s.lfi_base = W::far + F::lfi; s.lfi_stride = C::NLF; s.lsi_base = W::far + F::lsi; s.lsi_stride = C::NLS; s.lsi_sb = C::SB;
-        };
-        // (these offsets lie in front of everything that depends on the workgroup size or on ROWS / SOFT)
-        if (h->use_qp3 == 3 && h->jit) {   // a run-time instantiated shape: the offsets its own info kernel reported
-            const int* o = h->jit->fbo;
-            s.kind = 3; s.k_base = o[0]; s.k_stride = o[1]; s.lji_base = 0; s.lji_stride = 0;
-            s.lfi_base = o[2]; s.lfi_stride = o[3]; s.lsi_base = o[4]; s.lsi_stride = o[5]; s.lsi_sb = o[6];
-        }
-        else if (h->use_qp3 == 1) fill(upr_qp3_cfg<9, 1, 4, 3, 20, 256>());
-#define X(a, b, c, e, n, rows, sf, dense) else if (qp3_match(h->P, h->d, a, b, c, e, n, rows, sf, dense)) fill(upr_qp3_cfg<a, b, c, e, n, 256, rows, sf, dense>());
-        UPR_QP3_EXTRA(X)
-#undef X
-        return s;
-    }
-    if (h->use_qp2) {
-#define X(a, b, c, e) if (h->P.nq == a && h->P.nb == b && h->P.nc == c && h->P.nf == e) { typedef upr_qp2_dims<a, b, c, e> D; upr_qp2_ws<D> w(d.N, d.neN); \
-        s.kind = 2; s.k_base = w.store + D::SS_V; s.k_stride = D::SS_STRIDE; s.lji_base = w.store + D::SS_LJI; s.lji_stride = D::SS_STRIDE; \
-        s.lfi_base = w.pre + D::PR_LFI; s.lfi_stride = D::PR_STRIDE; s.lsi_base = w.pre + D::PR_LSI; s.lsi_stride = D::PR_STRIDE; s.lsi_sb = d.ne; return s; }
-        UPR_QP2_SHAPES(X)
-#undef X
-    }
-    s.kind = 1; s.k_base = d.ws_store + d.ss_kx; s.k_stride = d.ss_stride; s.lji_base = d.ws_store + d.ss_hjj; s.lji_stride = d.ss_stride;
-    s.lfi_base = d.ws_store + d.ss_hff; s.lfi_stride = d.ss_stride; s.lsi_base = d.ws_store + d.ss_sinv; s.lsi_stride = d.ss_stride; s.lsi_sb = d.ne;
-    return s;
-}
-
 // Longest-first dispatch of the QP launch.  One workgroup solves one instance and a launch of B instances runs on
 // 2 x 256 workgroup slots, so its duration is set by the slot that draws the largest SUM of IPM iteration counts: with
 // the headline's 10..13 iterations per instance, arrival order gives 25 on some slot against a mean of 22.7.  The
@@ -861,7 +768,7 @@ int advance_impl(upr_batch* h) {
         {
             upr_qp_args Q = make_qp_args(h);
             // the production kernel writes the feedback gains of the advance's LAST QP itself (no gather kernel afterwards)
-            if (h->fb && h->fb_fused && it == sqp_iters - 1) Q.fb = h->fb;
+            if (h->fb && h->qp.fb_fused && it == sqp_iters - 1) Q.fb = h->fb;
             if (h->order_on && h->order_valid) Q.order = h->order;
             KernelTimer T(h, 1); if (launch_qp(h, Q)) return 1; T.stop();
         }
@@ -875,10 +782,10 @@ int advance_impl(upr_batch* h) {
         { KernelTimer T(h, 2); int rc = (h->P.nq == 6) ? launch_linesearch<6>(h, L) : launch_linesearch<9>(h, L); if (rc) return 1; T.stop(); }
         if (h->order_on) h->order_valid = true;
     }
-    if (h->fb && !(h->fb_fused && sqp_iters > 0)) {   // sqp.use_feedback_policy: gains of the last QP, before anything overwrites its factors
-        if (fb_source(h).kind == 0) return fail("feedback gains: the selected QP kernel names no source for them");
-        if (d.ne <= 6 && d.nfc <= 12) hipLaunchKernelGGL((feedback_kernel<6, 12>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, fb_source(h), h->ws, h->lin, h->Df, h->stats, h->fb);
-        else hipLaunchKernelGGL((feedback_kernel<6 * UPR_MAX_BODIES, 3 * UPR_MAX_CONTACTS>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, fb_source(h), h->ws, h->lin, h->Df, h->stats, h->fb);
+    if (h->fb && !(h->qp.fb_fused && sqp_iters > 0)) {   // sqp.use_feedback_policy: gains of the last QP, before anything overwrites its factors
+        if (h->qp.fb.kind == 0) return fail("feedback gains: the selected QP kernel names no source for them");
+        if (d.ne <= 6 && d.nfc <= 12) hipLaunchKernelGGL((feedback_kernel<6, 12>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->qp.fb, h->ws, h->lin, h->Df, h->stats, h->fb);
+        else hipLaunchKernelGGL((feedback_kernel<6 * UPR_MAX_BODIES, 3 * UPR_MAX_CONTACTS>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->qp.fb, h->ws, h->lin, h->Df, h->stats, h->fb);
         UPR_HIP(hipGetLastError());
     }
     h->hdyn_prev = h->hdyn0;
@@ -950,42 +857,25 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
     h->hdyn0.assign((size_t)B * 9 * P->n_dyn, 0.0); h->hdyn_prev = h->hdyn0; h->htprev.assign(B, 0.0);
     const upr_dims& d = h->d;
     if (d.nx > UPR_LPK) { fail("nx exceeds the 32 tangent lanes of the linearisation kernel"); delete h; return nullptr; }
-    // collision rows (state-polytopic inequalities) are implemented in the generic kernel only
-    const bool soft = P->soft_state_box || P->soft_input_box || P->soft_poly || P->soft_eq;
-    const bool plain = h->d.no == 0 && !soft;   // rows the second-structure kernel does not have
-    h->use_qp3 = qp3_variant(*P, h->d);
-    h->use_qp2 = qp2_has_shape(*P) && plain;
-    const bool forced_other = (getenv("UPR_QP_KERNEL") && atoi(getenv("UPR_QP_KERNEL")) < 3) || (getenv("UPR_QP_GENERIC") && atoi(getenv("UPR_QP_GENERIC")) != 0);
-    if (getenv("UPR_QP3_JIT") && atoi(getenv("UPR_QP3_JIT")) == 2) h->use_qp3 = 0;   // (diagnostic: the run-time instantiation also for the listed shapes)
-    if (h->use_qp3 == 0 && !forced_other && jit_wanted(B) && jit_capable(*P, h->d)) {
-        // a shape outside the list: instantiate the production structure for it now (falls back with a note if that fails)
-        upr_jit_kernel* k = nullptr;
-        if (jit_get(*P, h->d, &k) == 0) { h->use_qp3 = 3; h->jit = k; }
-        else fprintf(stderr, "libupright_mi: %s -- using the %s kernel instead\n", g_err.c_str(), h->use_qp2 ? "second-structure" : "generic");
-    }
-    // UPR_QP_KERNEL = 1 (generic) | 2 | 3 selects an older structure for A/B measurements and tests
-    if (const char* e = getenv("UPR_QP_KERNEL")) { int v = atoi(e); if (v < 3) h->use_qp3 = 0; if (v < 2) h->use_qp2 = false; }
-    if (const char* e = getenv("UPR_QP_GENERIC")) { if (atoi(e) != 0) { h->use_qp2 = false; h->use_qp3 = 0; } }
-    h->qp_nt = h->use_qp3 ? 256 : 128;
-    if (const char* e = getenv("UPR_QP_NT")) h->qp_nt = atoi(e);
-    if (h->use_qp3 == 2) h->qp_nt = 256;
-    h->fb_fused = h->use_qp3 != 0;
-    if (const char* e = getenv("UPR_FB_FUSED")) h->fb_fused = h->fb_fused && atoi(e) != 0;
-    {   // every QP kernel indexes the instance workspace with the same stride: the largest any selectable one needs
-        size_t need = qp2_ws_doubles(*P, h->d);
-        if ((size_t)h->d.ws_stride < need) h->d.ws_stride = (int)need;
-        if (h->use_qp3) { need = (h->use_qp3 == 3) ? h->jit->ws : qp3_ws_doubles(*P, h->d, h->use_qp3); if ((size_t)h->d.ws_stride < need) h->d.ws_stride = (int)need; }
-    }
-    {
-        char buf[128];
-        if (h->use_qp3 == 1) snprintf(buf, sizeof(buf), "upr_qp3_kernel<upr_qp3_cfg<9, 1, 4, 3, 20, %d, %s, false, false>>", h->qp_nt, h->d.no > 0 ? "true" : "false");
-#define X(a, b, c, e, n, rows, sf, dense) else if (h->use_qp3 == 2 && qp3_match(*P, h->d, a, b, c, e, n, rows, sf, dense)) snprintf(buf, sizeof(buf), "upr_qp3_kernel<upr_qp3_cfg<%d, %d, %d, %d, %d, 256, %s, %s, %s>>", a, b, c, e, n, #rows, #sf, #dense);
-        UPR_QP3_EXTRA(X)
-#undef X
-        else if (h->use_qp3 == 3) snprintf(buf, sizeof(buf), "upr_qp3_jit<upr_qp3_cfg<%s>>", h->jit->cfg.c_str());
-        else if (h->use_qp2) snprintf(buf, sizeof(buf), "upr_qp2_kernel<upr_qp2_dims<%d, %d, %d, %d>, %d>", P->nq, P->nb, P->nc, P->nf, h->qp_nt == 512 ? 128 : h->qp_nt);
-        else snprintf(buf, sizeof(buf), "upr_qp_kernel<%d>", generic_nt(h));
-        h->qp_name = buf;
+    {   // the QP kernel of this handle (upr_qp_select.h): planned from the problem and the knobs, a run-time instantiation made where the
+        // plan asks for one, then resolved into the record every later site reads
+        upr_qp_knobs k;
+        if (const char* e = getenv("UPR_QP_KERNEL")) k.qp_kernel = atoi(e);
+        if (const char* e = getenv("UPR_QP_GENERIC")) k.qp_generic = atoi(e) != 0;
+        if (const char* e = getenv("UPR_QP3_JIT")) k.qp3_jit = atoi(e);
+        if (const char* e = getenv("UPR_QP_NT")) { k.qp_nt_set = true; k.qp_nt = atoi(e); }
+        if (const char* e = getenv("UPR_QP_GENERIC_NT")) { k.generic_nt_set = true; k.generic_nt = atoi(e); }
+        if (const char* e = getenv("UPR_JIT_NT")) k.jit_nt = atoi(e);
+        if (const char* e = getenv("UPR_FB_FUSED")) k.fb_fused = atoi(e) != 0;
+        upr_qp_sel& s = h->qp;
+        static_cast<upr_qp_choice&>(s) = upr_qp_plan(*P, d, k);
+        if (s.source == UPR_QP_FROM_RUN_TIME && s.structure == UPR_QP_STRUCT_PRODUCTION && jit_get(s.cfg, s.nt, &s.jit) != 0) {
+            // a shape outside the list whose instantiation failed: falls back with a note
+            static_cast<upr_qp_choice&>(s) = upr_qp_plan(*P, d, k, false);
+            fprintf(stderr, "libupright_mi: %s -- using the %s kernel instead\n", g_err.c_str(), s.structure == UPR_QP_STRUCT_SECOND ? "second-structure" : "generic");
+        }
+        qp_resolve(s, *P, d);
+        h->d.ws_stride = s.ws_stride;
     }
     if (const char* e = getenv("UPR_LIN_MFMA")) h->use_mfma = atoi(e) != 0;
     if (const char* e = getenv("UPR_LIN2")) h->lin2 = atoi(e) != 0;
@@ -1183,7 +1073,7 @@ static int get_feedback_core(upr_batch* h, double* K) {
 
 double upr_batch_last_solve_ms(const upr_batch* h) { return h ? h->last_ms : 0.0; }
 
-const char* upr_batch_qp_kernel_name(const upr_batch* h) { return h ? h->qp_name.c_str() : ""; }
+const char* upr_batch_qp_kernel_name(const upr_batch* h) { return h ? h->qp.name : ""; }
 
 const char* upr_batch_ls_kernel_name(upr_batch* h) {
     if (!h || h->ls_form[4] < 0) return "";
@@ -1323,17 +1213,12 @@ int upr_batch_eq_input_jacobian(upr_batch* h, int inst, double* gu) {
     return 0;
 }
 
-// does the QP kernel of this handle carry slack pairs (sigma, tau, gam) of softened inequality rows, and where: the SOFT
-// instantiations of the production kernel export them behind the slacks, the generic kernel keeps them in the instance workspace
-static bool vf_has_pairs(const upr_batch* h) { return h->d.soft && (h->use_qp3 ? needs_soft(h->P, h->d) : !h->use_qp2); }
-
 // linearise at the current trajectory and solve one QP there with the multiplier export (no synchronisation)
 static int kkt_launch(upr_batch* h) {
-    const int kdoubles = upr_kkt_doubles(h->d);
-    if (h->use_qp3 && !h->kkt && dev_alloc(&h->kkt, (size_t)h->B * kdoubles)) return 1;
+    if (h->qp.exported && !h->kkt && dev_alloc(&h->kkt, (size_t)h->B * h->qp.stride)) return 1;
     if (do_linearize(h, traj_lin_args(h))) return 1;
     upr_qp_args A = make_qp_args(h);
-    if (h->use_qp3) { A.kkt = h->kkt; A.kkt_stride = kdoubles; }
+    if (h->qp.exported) { A.kkt = h->kkt; A.kkt_stride = h->qp.stride; }
     return launch_qp(h, A);
 }
 
@@ -1362,30 +1247,22 @@ int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double*
     if (h->P.n_dyn) return fail("upr_batch_qp_kkt: not available with a dynamic obstacle (interface states)");
     const upr_dims& d = h->d;
     if (ni_out) *ni_out = d.ni_stage;
-    const int kdoubles = upr_kkt_doubles(d);
+    const upr_qp_sel& sel = h->qp;   // (where the selected kernel left the primal-dual point: the export buffer or the workspace)
     if (kkt_launch(h)) return 1;
     UPR_HIP(hipStreamSynchronize(h->stream));
     std::vector<double> ws((size_t)h->B * d.ws_stride), kk;
     UPR_HIP(hipMemcpy(ws.data(), h->ws, sizeof(double) * ws.size(), hipMemcpyDeviceToHost));
-    if (h->use_qp3) { kk.resize((size_t)h->B * kdoubles); UPR_HIP(hipMemcpy(kk.data(), h->kkt, sizeof(double) * kk.size(), hipMemcpyDeviceToHost)); }
+    if (sel.exported) { kk.resize((size_t)h->B * sel.stride); UPR_HIP(hipMemcpy(kk.data(), h->kkt, sizeof(double) * kk.size(), hipMemcpyDeviceToHost)); }
     const int n1 = d.N + 1;
-    int o_pi = d.ws_pi, o_nu = d.ws_nu, o_y = d.ws_yN, o_lam = d.ws_lam, o_t = d.ws_t;
-    if (!h->use_qp3 && h->use_qp2) {
-#define X(a, b, c, e) if (h->P.nq == a && h->P.nb == b && h->P.nc == c && h->P.nf == e) { upr_qp2_ws<upr_qp2_dims<a, b, c, e>> w(d.N, d.neN); o_pi = w.pi; o_nu = w.nu; o_y = w.yN; o_lam = w.lam; o_t = w.t; }
-        UPR_QP2_SHAPES(X)
-#undef X
-    }
     for (int b = 0; b < h->B; ++b) {
         const double* w = ws.data() + (size_t)b * d.ws_stride;
         if (dxs) std::memcpy(dxs + (size_t)b * n1 * d.nx, w + d.ws_dx, sizeof(double) * n1 * d.nx);
         if (dus) std::memcpy(dus + (size_t)b * d.N * d.nu, w + d.ws_du, sizeof(double) * d.N * d.nu);
-        const double *spi, *snu, *sy, *sl, *st;
         const size_t nsl = (size_t)n1 * d.ni_stage;
+        const double* m = (sel.exported ? kk.data() : ws.data()) + (size_t)b * sel.stride;
+        const double *spi = m + sel.o_pi, *snu = m + sel.o_nu, *sy = m + sel.o_yN, *sl = m + sel.o_lam, *st = m + sel.o_t;
         const double* sp[3] = {nullptr, nullptr, nullptr};   // sigma, tau, gam of the softened rows (problems that have some)
-        if (h->use_qp3) { const double* k = kk.data() + (size_t)b * kdoubles; spi = k; snu = spi + n1 * d.nx; sy = snu + d.N * d.ne; sl = sy + d.neN; st = sl + nsl;
-                          if (vf_has_pairs(h)) for (int q = 0; q < 3; ++q) sp[q] = st + (q + 1) * nsl; }
-        else { spi = w + o_pi; snu = w + o_nu; sy = w + o_y; sl = w + o_lam; st = w + o_t;
-               if (vf_has_pairs(h)) { sp[0] = w + d.ws_sig; sp[1] = w + d.ws_tau; sp[2] = w + d.ws_gam; } }
+        if (sel.o_sig >= 0) { sp[0] = m + sel.o_sig; sp[1] = m + sel.o_tau; sp[2] = m + sel.o_gam; }
         if (b == 0) {
             h->kkt_slack.assign((size_t)h->B * nsl, 1.0);
             h->kkt_pairs.assign(3 * (size_t)h->B * nsl, 0.0);
@@ -1456,21 +1333,9 @@ int upr_batch_value_function_update(upr_batch* h) {
     if (kkt_launch(h)) return 1;
     upr_vf_args A;
     A.P = h->dP; A.d = d; A.xs = h->xs; A.us = h->us; A.lin = h->lin; A.Df = h->Df; A.ws = h->ws;
-    const int nsl = (int)n1 * d.ni_stage;
-    if (h->use_qp3) {
-        A.mult = h->kkt; A.mult_stride = upr_kkt_doubles(d);
-        A.o_pi = 0; A.o_nu = (int)(n1 * nx); A.o_lam = A.o_nu + d.N * d.ne + d.neN; A.o_t = A.o_lam + nsl;
-        A.o_sig = A.o_t + nsl; A.o_tau = A.o_sig + nsl; A.o_gam = A.o_tau + nsl;
-    } else {
-        A.mult = h->ws; A.mult_stride = d.ws_stride;
-        A.o_pi = d.ws_pi; A.o_nu = d.ws_nu; A.o_lam = d.ws_lam; A.o_t = d.ws_t; A.o_sig = d.ws_sig; A.o_tau = d.ws_tau; A.o_gam = d.ws_gam;
-        if (h->use_qp2) {
-#define X(a, b, c, e) if (h->P.nq == a && h->P.nb == b && h->P.nc == c && h->P.nf == e) { upr_qp2_ws<upr_qp2_dims<a, b, c, e>> w(d.N, d.neN); A.o_pi = w.pi; A.o_nu = w.nu; A.o_lam = w.lam; A.o_t = w.t; }
-            UPR_QP2_SHAPES(X)
-#undef X
-        }
-    }
-    if (!vf_has_pairs(h)) A.o_sig = A.o_tau = A.o_gam = -1;
+    const upr_qp_sel& q = h->qp;
+    A.mult = q.exported ? h->kkt : h->ws; A.mult_stride = q.stride;
+    A.o_pi = q.o_pi; A.o_nu = q.o_nu; A.o_lam = q.o_lam; A.o_t = q.o_t; A.o_sig = q.o_sig; A.o_tau = q.o_tau; A.o_gam = q.o_gam;
     A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X;
     if (lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)upr_value_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     UPR_HIP(hipEventRecord(h->vf_ev[0], h->stream));
@@ -1544,7 +1409,7 @@ int upr_batch_qp_profile(upr_batch* h, double* out) {
     UPR_ENTER(h);
     {
         const char* f = getenv("UPR_JIT_FLAGS");
-        if (h->use_qp3 != 3 || !f || !strstr(f, "-DUPR_QP3_PROF"))
+        if (!h->qp.jit || !f || !strstr(f, "-DUPR_QP3_PROF"))
             return fail("upr_batch_qp_profile: the phase stamps exist in run-time instantiations only: create the handle with UPR_QP3_JIT=2 UPR_JIT_FLAGS=-DUPR_QP3_PROF");
     }
     if (!h->prof) { if (dev_alloc(&h->prof, (size_t)h->B * 64)) return 1; return 0; }
@@ -1746,8 +1611,8 @@ int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x,
     const int sqp_now = h->sqp_iters_next > 0 ? h->sqp_iters_next : h->P.sqp_iters;
     unsigned long long sig = 1469598103934665603ull;
     for (unsigned long long v : {(unsigned long long)h->has_prev, (unsigned long long)h->guess_set, (unsigned long long)sqp_now, (unsigned long long)(h->order_on && h->order_valid),
-                                 (unsigned long long)(h->fb != nullptr), (unsigned long long)h->fb_fused, (unsigned long long)h->timing, (unsigned long long)(stats_out != nullptr),
-                                 (unsigned long long)h->use_qp3, (unsigned long long)h->use_qp2, (unsigned long long)h->qp_nt, (unsigned long long)(uintptr_t)h->pin,
+                                 (unsigned long long)(h->fb != nullptr), (unsigned long long)h->qp.fb_fused, (unsigned long long)h->timing, (unsigned long long)(stats_out != nullptr),
+                                 (unsigned long long)h->qp.structure, (unsigned long long)h->qp.source, (unsigned long long)h->qp.nt, (unsigned long long)(uintptr_t)h->pin,
                                  (unsigned long long)(uintptr_t)h->prof /* (passed BY VALUE in upr_qp_args: a graph captured before upr_batch_qp_profile allocated it would keep nullptr) */}) { sig ^= v; sig *= 1099511628211ull; }
     const bool steady = h->tick_graph_on && !h->timing && h->has_prev && !h->guess_set && h->sqp_iters_next == 0 && (!h->order_on || h->order_valid);
     if (steady && h->tick_exec && sig == h->tick_sig) {

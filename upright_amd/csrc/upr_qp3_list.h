@@ -4,7 +4,7 @@
 // (9, 1, 4, 3; N = 20; hard rows) with and without state-polytopic rows: Y(NT, ROWS).  (Rounds 1 - 5 also shipped it at 128 and 512
 // lanes for A/B runs: both slower, 512 - 655 spilled registers, selected by nothing but UPR_QP_NT -- dropped in round 6;
 // UPR_JIT_NT still instantiates them at run time for an experiment.)
-// A problem takes the FIRST entry of UPR_QP3_EXTRA that matches it (upr_api.hip, qp3_match).
+// A problem takes the FIRST entry of UPR_QP3_EXTRA that matches it (upr_qp_select.h, upr_qp3_match).
 #pragma once
 
 // (nq, nb, nc, nf, ROWS, SOFT, DENSE) instantiations besides the headline's: the headline shape with slacks on its boxes,
