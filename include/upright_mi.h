@@ -333,6 +333,10 @@ const char* upr_batch_qp_kernel_name(const upr_batch* h);
 /* name of the line-search kernel instantiation the handle's last line-search launch ran (upr_linesearch_kernel<NQ, NT, NFM, NBM,
  * EXACT, OBS, STAGE>, as rocprofv3 prints it); "" before the first advance */
 const char* upr_batch_ls_kernel_name(upr_batch* h);
+/* name of the linearisation kernel instantiation the handle's last linearisation launch ran, in trajectory or points mode:
+ * upr_linearize_kernel<NQ, USE_MFMA, OCC, ORI, NPASS> with every argument written out, or upr_linearize2_kernel<NQ> followed by
+ * " kpw=<knots per workgroup> blocks=<workgroups>" of that launch; "" before the first launch */
+const char* upr_batch_lin_kernel_name(upr_batch* h);
 int upr_batch_device(const upr_batch* h);   /* the HIP device the handle lives on; -1 for a null handle */
 /* doubles of device workspace per instance (QP result, multipliers, the QP kernel's far arrays): what an instance writes once and
  * re-streams every interior-point iteration -- bench.py's model of the compulsory DRAM traffic of a launch */

@@ -19,7 +19,8 @@ p = _capi.ptr
 
 
 class Emu:
-    def __init__(self, P, B):
+    def __init__(self, P, B, bp=None):
+        """bp: inertial parameters per instance [B][nb][10] (default: the problem's own for every instance)"""
         self.P, self.B = P, B
         self.E = C.CDLL(str(EMU))
         for f in ("emu_qp2", "emu_qp3"):
@@ -29,7 +30,7 @@ class Emu:
         self.E.emu_dims(C.byref(self.cp), d)
         (self.nx, self.nu, self.ne, self.np_, self.lin_stride, self.ws_stride, self.ws_dx, self.ws_du, self.lin_g, self.lin_gx,
          self.lin_cost, self.lin_grad, self.lin_hess, self.nfc) = list(d)[:14]
-        self.bp = np.ascontiguousarray(np.broadcast_to(P.body_params, (B,) + P.body_params.shape))
+        self.bp = np.ascontiguousarray(np.broadcast_to(P.body_params, (B,) + P.body_params.shape) if bp is None else np.asarray(bp, dtype=np.float64).reshape((B,) + P.body_params.shape))
         self.Df = np.zeros((B, self.ne, self.nfc))
         self.E.emu_make_Df(C.byref(self.cp), B, p(self.bp), p(self.Df))
 
@@ -656,6 +657,61 @@ def test_every_qp_instantiation_has_a_screen_case():
     arr = json.load(open(Path(__file__).resolve().parent / "golden" / "arrangements.json"))
     forms = {GOLDEN_LS[n][1] if n in GOLDEN_LS else ls_case(arr, n)["form"] for n in DEVICE_CASES}
     assert forms == {EXACT, EXACT_ROWS, SMALL, LARGE}, forms
+
+
+def _launch_linearize_forms():
+    """Every kernel instantiation launch_linearize (upr_api.hip) names, at both chain lengths, in the form notation of
+    tests/test_gpu_lin_screen.py: ("lin2", NQ) and ("lin", NQ, USE_MFMA, OCC, ORI, NPASS) with the template's defaults
+    (upr_linearize.h: OCC = 2, ORI = false, NPASS = 1) and UPR_LIN_PASSES filled in."""
+    import re
+    csrc = Path(__file__).resolve().parents[1] / "upright_amd" / "csrc"
+    text = (csrc / "upr_api.hip").read_text()
+    body = text.split("int launch_linearize(upr_batch* h, const upr_lin_args& A) {", 1)[1].split("\ntypedef int (*upr_qp_launcher)", 1)[0]
+    header = (csrc / "upr_linearize.h").read_text()
+    passes = int(re.search(r"#define\s+UPR_LIN_PASSES\s+(\d+)", header).group(1))
+    assert re.search(r"template <int NQ, bool USE_MFMA, int OCC = 2, bool ORI = false, int NPASS = 1>\s*__global__ void __launch_bounds__\(256, OCC\) upr_linearize_kernel", header)
+    flag = {"true": True, "false": False}
+    forms, sites = set(), 0
+    for name, args in re.findall(r"\b(upr_linearize2?_kernel)<([^>]*)>", body):
+        a = [w.strip() for w in args.split(",")]
+        assert a[0] == "NQ", (name, args)
+        sites += 1
+        for nq in (6, 9):
+            if name == "upr_linearize2_kernel":
+                assert len(a) == 1
+                forms.add(("lin2", nq))
+            else:
+                t = a[1:] + ["2", "false", "1"][len(a) - 2:]
+                forms.add(("lin", nq, flag[t[0]], int(t[1]), flag[t[2]], passes if t[3] == "UPR_LIN_PASSES" else int(t[3])))
+    assert re.search(r"\(h->P\.nq == 6\) \? launch_linearize<6>\(h, A\) : launch_linearize<9>\(h, A\)", text)
+    return forms, sites
+
+
+def test_every_linearisation_form_has_a_screen_case():
+    """Coverage guard of tests/test_gpu_lin_screen.py: every kernel instantiation launch_linearize can pick, at NQ 6 and 9, is the
+    form of a case of the screen's table, the table names no form the launcher lacks, and the cases the screen was specified with
+    are all there -- an instantiation added to the launcher, or a case deleted from the table, fails here before any GPU time."""
+    import sys
+    sys.path.insert(0, str(Path(__file__).resolve().parent))
+    from test_gpu_lin_screen import CASES, KNOBS
+
+    forms, sites = _launch_linearize_forms()
+    assert sites == 10 and len(forms) == 18, (sites, sorted(forms))   # upr_linearize2_kernel + nine launches of eight instantiations
+    table = {tuple(v[3]) for v in CASES.values()}
+    assert not forms - table, "instantiations without a screen case: %s" % sorted(forms - table)
+    assert not table - forms, "cases whose form launch_linearize does not have: %s" % sorted(table - forms)
+    required = ["headline_B37", "headline_B1024", "ur10_demo", "arm_only", "robust_N20", "robust_N100", "cups", "dice", "box_arch_rows",
+                "collision_rows", "thrown_ball", "two_obstacles", "box_only", "box_collision_rows", "orientation", "orientation_ur10",
+                "orientation_box", "headline_lin2_off", "collision_rows_lin2_off", "headline_no_mfma", "orientation_no_mfma"]
+    assert not [n for n in required if n not in CASES], [n for n in required if n not in CASES]
+    # the process-static knobs: both values of each, two cases per value, one at each chain length
+    assert KNOBS == [("UPR_LIN_OCC", "3"), ("UPR_LIN_OCC", "4"), ("UPR_LIN_ROW_PASSES", "1"), ("UPR_LIN_ROW_PASSES", "3")]
+    for knob in KNOBS:
+        assert sorted(v[3][1] for v in CASES.values() if v[4] == knob) == [6, 9], knob
+    # the row-pass forms are reached by a shape with collision rows, the multi-pass form by one without (same instantiation at 3 passes)
+    for nq in (6, 9):
+        with_rows = {bool(v[1].get("rows")) for v in CASES.values() if tuple(v[3]) == ("lin", nq, True, 2, False, 3)}
+        assert with_rows == {True, False}, (nq, with_rows)
 
 
 class _Knobs(C.Structure):

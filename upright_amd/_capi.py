@@ -156,6 +156,7 @@ PROTOTYPES = [
     ("upr_batch_enable_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("upr_batch_qp_kernel_name", C.c_char_p, [C.c_void_p]),
     ("upr_batch_ls_kernel_name", C.c_char_p, [C.c_void_p]),
+    ("upr_batch_lin_kernel_name", C.c_char_p, [C.c_void_p]),
     ("upr_batch_copy_solution_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("upr_batch_copy_policy_device", C.c_int, [C.c_void_p, C.c_void_p]),
     ("upr_set_device", C.c_int, [C.c_int]),

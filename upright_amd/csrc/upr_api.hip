@@ -309,6 +309,9 @@ struct upr_batch {
     hipEvent_t vf_ev[2] = {nullptr, nullptr};
     std::string ls_name;   // the line-search kernel instantiation of the handle's last line-search launch (upr_batch_ls_kernel_name)
     int ls_form[5] = {0, 0, 0, 0, -1};   // (NFM, NBM, EXACT, OBS, STAGE) of that launch; STAGE -1: no line search launched yet
+    std::string lin_name;   // the linearisation kernel instantiation of the handle's last linearisation launch (upr_batch_lin_kernel_name)
+    // of that launch: kind (-1: none yet; 1: upr_linearize_kernel; 2: upr_linearize2_kernel), then (USE_MFMA, OCC, ORI, NPASS) or (kpw, blocks)
+    int lin_form[5] = {-1, 0, 0, 0, 0};
     std::vector<hipEvent_t> ev_pool, ev_free;   // events in use (pairs, in launch order) / harvested ones waiting for reuse
     std::vector<int> ev_slot;
 };
@@ -380,6 +383,7 @@ int launch_linearize(upr_batch* h, const upr_lin_args& A) {
         if (kpw >= 1) {
             const size_t lds2 = (size_t)(npre + kpw * lay.per) * sizeof(double);
             hipLaunchKernelGGL(upr_linearize2_kernel<NQ>, dim3((A.npoints + kpw - 1) / kpw), dim3(256), lds2, h->stream, A, kpw, h->P.n_sph);
+            h->lin_form[0] = 2; h->lin_form[1] = kpw; h->lin_form[2] = (A.npoints + kpw - 1) / kpw;
             UPR_HIP(hipGetLastError());
             return 0;
         }
@@ -391,20 +395,22 @@ int launch_linearize(upr_batch* h, const upr_lin_args& A) {
     // (rounds 1 - 2, one forward-mode walk per tangent lane: 2 -> 0.130 ms, 3 -> 0.142 ms, 4 -> 0.32 ms with spills; round 3, one value
     // walk per knot + closed-form tangents: 2 -> 0.091 ms, 3 -> 0.085 ms;
     // with the walks of three passes side by side: 2 -> 0.073 ms, 3 -> 0.095 ms)
-    auto launch = [&](void (*kern)(upr_lin_args)) -> int {
+    // (mfma, occ, ori, npass: the template arguments of kern besides NQ, remembered for upr_batch_lin_kernel_name)
+    auto launch = [&](void (*kern)(upr_lin_args), bool mfma, int o, bool ori, int npass) -> int {
         if (lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, h->stream, A);
+        h->lin_form[0] = 1; h->lin_form[1] = mfma; h->lin_form[2] = o; h->lin_form[3] = ori; h->lin_form[4] = npass;
         return 0;
     };
     int rc;
-    if (A.way_q) rc = h->use_mfma ? launch(upr_linearize_kernel<NQ, true, 2, true>) : launch(upr_linearize_kernel<NQ, false, 2, true>);   // end-effector cost with orientation weights
-    else if (!h->use_mfma) rc = launch(upr_linearize_kernel<NQ, false>);
-    else if (occ == 3) rc = launch(upr_linearize_kernel<NQ, true, 3>);
-    else if (occ == 4) rc = launch(upr_linearize_kernel<NQ, true, 4>);
-    else if (multi) rc = launch(upr_linearize_kernel<NQ, true, 2, false, UPR_LIN_PASSES>);
-    else if (multi_rows && row_passes == 3) rc = launch(upr_linearize_kernel<NQ, true, 2, false, 3>);
-    else if (multi_rows) rc = launch(upr_linearize_kernel<NQ, true, 2, false, 2>);
-    else rc = launch(upr_linearize_kernel<NQ, true>);
+    if (A.way_q) rc = h->use_mfma ? launch(upr_linearize_kernel<NQ, true, 2, true>, true, 2, true, 1) : launch(upr_linearize_kernel<NQ, false, 2, true>, false, 2, true, 1);   // end-effector cost with orientation weights
+    else if (!h->use_mfma) rc = launch(upr_linearize_kernel<NQ, false>, false, 2, false, 1);
+    else if (occ == 3) rc = launch(upr_linearize_kernel<NQ, true, 3>, true, 3, false, 1);
+    else if (occ == 4) rc = launch(upr_linearize_kernel<NQ, true, 4>, true, 4, false, 1);
+    else if (multi) rc = launch(upr_linearize_kernel<NQ, true, 2, false, UPR_LIN_PASSES>, true, 2, false, UPR_LIN_PASSES);
+    else if (multi_rows && row_passes == 3) rc = launch(upr_linearize_kernel<NQ, true, 2, false, 3>, true, 2, false, 3);
+    else if (multi_rows) rc = launch(upr_linearize_kernel<NQ, true, 2, false, 2>, true, 2, false, 2);
+    else rc = launch(upr_linearize_kernel<NQ, true>, true, 2, false, 1);
     if (rc) return rc;
     UPR_HIP(hipGetLastError());
     return 0;
@@ -1082,6 +1088,16 @@ const char* upr_batch_ls_kernel_name(upr_batch* h) {
     snprintf(buf, sizeof(buf), "upr_linesearch_kernel<%d, 128, %d, %d, %s, %s, %s>", h->P.nq, f[0], f[1], f[2] ? "true" : "false", f[3] ? "true" : "false", f[4] ? "true" : "false");
     h->ls_name = buf;
     return h->ls_name.c_str();
+}
+
+const char* upr_batch_lin_kernel_name(upr_batch* h) {
+    if (!h || h->lin_form[0] < 0) return "";
+    const int* f = h->lin_form;
+    char buf[128];
+    if (f[0] == 2) snprintf(buf, sizeof(buf), "upr_linearize2_kernel<%d> kpw=%d blocks=%d", h->P.nq, f[1], f[2]);
+    else snprintf(buf, sizeof(buf), "upr_linearize_kernel<%d, %s, %d, %s, %d>", h->P.nq, f[1] ? "true" : "false", f[2], f[3] ? "true" : "false", f[4]);
+    h->lin_name = buf;
+    return h->lin_name.c_str();
 }
 
 /* restore == 0: keep a copy of the per-instance statistics and of the QP dispatch keys of the last advance; restore != 0: put that
