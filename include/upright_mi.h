@@ -283,7 +283,9 @@ int upr_batch_qp_step(upr_batch* h, double* dxs, double* dus);
  * costates of the dynamics (pi_0 unused), nu[B][N][ne] multipliers of the object-dynamics rows, yN[B][3 + 2 nq] of the
  * terminal equality, lam[B][N+1][ni] of the inequality rows with ni = 2 nx + 2 nu + np + no in the slot order
  * [x lower][x upper][u lower][u upper][friction rows][state rows: collision pairs, projectile rows, end-effector box upper 3,
- * lower 3]; *ni_out = ni.  Pointers may be NULL. */
+ * lower 3]; *ni_out = ni.  Pointers may be NULL.
+ * With dynamic obstacles (n_dyn > 0) dxs has the interface width, dxs[B][N+1][nx + 9 n_dyn], with a zero obstacle block as
+ * upr_batch_qp_step returns it (the obstacle is data of the QP); pi keeps the robot block, pi[B][N+1][nx]. */
 int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double* nu, double* yN, double* lam, int* ni_out);
 /* Slacks t[B][N+1][ni] of the inequality rows at the exit of the QP the last upr_batch_qp_kkt call solved (slot order of lam; 1 in
  * slots that are not rows of the knot).  lam / t are the barrier weights of the last interior-point iterate: with the costates they
@@ -303,18 +305,39 @@ int upr_batch_qp_slack_pairs(upr_batch* h, double* sigma, double* tau, double* g
  *   upr_batch_value_function_update  linearises at the current plan, solves one QP there with the multiplier export and runs the
  *       cost-to-go kernel (upright_amd/csrc/upr_value.h): P_k, p_k, J_k and the expansion points X_k of every instance and knot stay
  *       in device memory.  Softened inequality rows enter with the weight above, a softened equality with S = Df Hff^-1 Df' + I / Z.
- *       Statistics and QP dispatch keys of the last advance are put back afterwards (as upr_batch_hold_stats does).  Not available
- *       with dynamic obstacles.
+ *       Statistics and QP dispatch keys of the last advance are put back afterwards (as upr_batch_hold_stats does).  Every query
+ *       behind it has robot-state shapes: a handle with dynamic obstacles is refused, as before.
+ *   upr_batch_value_function_update_interface  the same update for any handle, dynamic obstacles included: the caller accepts the
+ *       interface-state convention of upr_batch_value_function below.  Without a dynamic obstacle the two entries are one.
+ *   upr_batch_track_value_function(h, on)  tracked mode: every advance and tick with at least one SQP iteration hands ITS OWN last QP
+ *       to the cost-to-go kernel, in-stream between that QP launch and its line search: no second linearisation, no extra QP, no
+ *       synchronisation.  The expansion point X_k = xs_lin + dx is that QP's solution -- ocs2's getValueFunction semantics: with a
+ *       line-search step alpha < 1 the plan the advance stores differs from X.  (upr_batch_value_function_update describes the QP at
+ *       the finished plan instead: one SQP iteration past it.)  Switching on allocates the buffers; never call it inside an advance
+ *       (between upr_batch_advance_async and upr_batch_sync).  A tracked cost-to-go belongs to the solve: it stays valid across
+ *       upr_batch_set_observation until the next advance or tick replaces it; upr_batch_reset, upr_batch_reset_async,
+ *       upr_batch_set_guess and switching tracking off make it stale.  A tick's captured graph carries the kernel and the copy of
+ *       the plan's time as two more nodes of its one chain.
  *   upr_batch_value_function  V[n] and dVdx[n][nx] at n points (inst[n], t[n], x[n][nx]):
  *       V(t, x) = J + p'(x - X) + 1/2 (x - X)'P (x - X),  dV/dx = p + P (x - X), of the two knots around t, interpolated linearly in t
  *       (t is clamped to the plan's horizon).  Fails before the first update, and with "stale" once the plan or the observation
- *       changed since the update (advance, tick, reset, set_guess, set_observation).
- *   upr_batch_get_cost_to_go  Pk[B][N+1][nx][nx], pk[B][N+1][nx], J[B][N+1], X[B][N+1][nx]; any pointer may be NULL.
- *   upr_batch_value_function_ms  device time (ms) of the last cost-to-go launch, HIP events around that launch only. */
+ *       changed since the update (advance, tick, reset, set_guess, set_observation).  With dynamic obstacles (n_dyn > 0) the points
+ *       are interface states, x[n][nx + 9 n_dyn], and dVdx[n][nx + 9 n_dyn] comes back with a ZERO obstacle block: the obstacle is
+ *       data of the QP the engine solves, not a state of its Riccati recursion.
+ *   upr_batch_equality_lagrangian  nu_out[n][ne] at n points (inst[n], t[n]): the multipliers of the object-dynamics rows of the
+ *       same QP (stateInputEqualityConstraintLagrangian, pybindings.cpp:409-412), piecewise linear between the knots; the last knot
+ *       carries none, so the last interval holds nu[N-1].  Same validity as upr_batch_value_function.
+ *   upr_batch_get_cost_to_go  Pk[B][N+1][nx][nx], pk[B][N+1][nx], J[B][N+1], X[B][N+1][nx]; any pointer may be NULL.  Robot-block shapes
+ *       with and without dynamic obstacles.
+ *   upr_batch_value_function_ms  device time (ms) of the last cost-to-go launch, HIP events around that launch only (a tracked launch
+ *       is timed only on a handle with upr_batch_enable_timing on; reading it waits for that launch). */
 int upr_batch_value_function_update(upr_batch* h);
+int upr_batch_value_function_update_interface(upr_batch* h);
+int upr_batch_track_value_function(upr_batch* h, int on);
+int upr_batch_equality_lagrangian(upr_batch* h, int n, const int* inst, const double* t, double* nu_out);
 int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double* t, const double* x, double* V, double* dVdx);
 int upr_batch_get_cost_to_go(upr_batch* h, double* Pk, double* pk, double* J, double* X);
-double upr_batch_value_function_ms(const upr_batch* h);
+double upr_batch_value_function_ms(upr_batch* h);
 
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):
  * xs (B*(N+1)*nx doubles) and us (B*N*nu doubles) */

@@ -148,6 +148,9 @@ PROTOTYPES = [
     ("upr_batch_qp_slacks", C.c_int, [C.c_void_p, dp]),
     ("upr_batch_qp_slack_pairs", C.c_int, [C.c_void_p, dp, dp, dp]),
     ("upr_batch_value_function_update", C.c_int, [C.c_void_p]),
+    ("upr_batch_value_function_update_interface", C.c_int, [C.c_void_p]),
+    ("upr_batch_track_value_function", C.c_int, [C.c_void_p, C.c_int]),
+    ("upr_batch_equality_lagrangian", C.c_int, [C.c_void_p, C.c_int, ip, dp, dp]),
     ("upr_batch_value_function", C.c_int, [C.c_void_p, C.c_int, ip, dp, dp, dp, dp]),
     ("upr_batch_get_cost_to_go", C.c_int, [C.c_void_p, dp, dp, dp, dp]),
     ("upr_batch_value_function_ms", C.c_double, [C.c_void_p]),

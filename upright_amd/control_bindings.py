@@ -585,38 +585,65 @@ class ControllerInterface:
     def _outside(self, name):
         raise RuntimeError(f"ControllerInterface.{name} is outside the accelerated path of the MI355X engine")
 
+    def _on_device(self):
+        """Which path answers the solver-level queries.  Hard inequality rows and no dynamic obstacle: the host module
+        (upright_amd/value_function.py, one instance in numpy).  HPIPM slacks on inequality rows (their barrier pairs enter the weights
+        the kernels factor) or a dynamic obstacle (interface states): the batched cost-to-go on the device, upr_value.h behind
+        BatchMPC.value_function_update() / value_function() / equality_lagrangian().  Same expansion point -- the QP at the plan the
+        last advanceMpc ended with -- and the same once-per-solve caching on both."""
+        sl = self.problem.slacks or {}
+        return bool(self.problem.n_dyn) or bool(sl.get("state_box") or sl.get("input_box") or sl.get("poly_ineq"))
+
+    def _need_solve(self):
+        if self._mpc is None or self._solves == 0:
+            raise RuntimeError("no MPC solve yet on the current target: call advanceMpc first"
+                               + (" (a problem with HPIPM slacks or dynamic obstacles is answered from the device's cost-to-go of that solve)" if self._on_device() else ""))
+
     def _value_function(self, riccati=True):
         """upright_amd/value_function.py: the Riccati cost-to-go of the QP at the plan the last advanceMpc ended with, rebuilt on the
         host from the primal-dual point the kernel exports (costates, multipliers and slacks); cached per solve."""
         from .value_function import ValueFunction
 
-        if self.problem.n_dyn:
-            raise RuntimeError("value function / Lagrangian queries are not available with dynamic obstacles (upr_batch_qp_kkt does not export the interface states' rows)")
-        sl = self.problem.slacks or {}
-        if riccati and (sl.get("state_box") or sl.get("input_box") or sl.get("poly_ineq")):
-            # a softened inequality row is factored with w0 (Z + gam / tau) / (Z + w0 + gam / tau), w0 = lam / t (upr_qp3.h row_soft); the
-            # kernels export (t, lam) only, so the cost-to-go rebuilt on the host would overstate the curvature of every active soft row
-            raise RuntimeError("value function queries need hard inequality rows: this problem carries HPIPM slacks "
-                               "(sqp.hpipm.slacks.{state_box, input_box, poly_ineq}) whose barrier pairs the engine does not export")
-        if self._mpc is None or self._solves == 0:
-            raise RuntimeError("no MPC solve yet on the current target: call advanceMpc first")
+        self._need_solve()
         if self._vf_key != self._solves or (riccati and self._vf.Pk is None):
             self._vf, self._vf_key = ValueFunction(self._mpc, 0, riccati=riccati), self._solves
         return self._vf
 
+    def _device_query(self, query):
+        """query(handle) on the device path: the cost-to-go is rebuilt at the first query after a solve, and again whenever the handle
+        reports it stale (something touched the plan or the observation since)."""
+        self._need_solve()
+        if self._vf_key != self._solves:
+            self._mpc.value_function_update(interface_states=True)
+            self._vf, self._vf_key = None, self._solves
+        try:
+            return query(self._mpc)
+        except RuntimeError as e:
+            if "stale" not in str(e):
+                raise
+            self._mpc.value_function_update(interface_states=True)
+            return query(self._mpc)
+
     def valueFunction(self, t, x):
         """pybindings.cpp:398-399 (ocs2 getValueFunction(t, x).f): cost-to-go of the plan from t, expanded to second order in x."""
+        if self._on_device():
+            return float(self._device_query(lambda m: m.value_function(float(t), np.asarray(x, dtype=np.float64), 0))[0][0])
         return float(self._value_function().value(t, x))
 
     def valueFunctionStateDerivative(self, t, x):
-        """pybindings.cpp:400-402 (ocs2 getValueFunction(t, x).dfdx): costate of the plan at t plus P(t) (x - x*(t))."""
+        """pybindings.cpp:400-402 (ocs2 getValueFunction(t, x).dfdx): costate of the plan at t plus P(t) (x - x*(t)); zero in the block
+        of a dynamic obstacle (data of the QP the engine solves)."""
+        if self._on_device():
+            return self._device_query(lambda m: m.value_function(float(t), np.asarray(x, dtype=np.float64), 0))[1][0].copy()
         g = np.zeros(self.problem.nx_full)
         g[:self.problem.nx] = self._value_function().gradient(t, x)
         return g
 
     def stateInputEqualityConstraintLagrangian(self, t, x, u):
         """pybindings.cpp:409-412: multipliers of the state-input equality (the object-dynamics rows) of the last QP at time t."""
-        return self._value_function(riccati=False).equality_multiplier(t).copy()   # (the multipliers alone: also with softened rows)
+        if self._on_device():
+            return self._device_query(lambda m: m.equality_lagrangian(np.array([float(t)]), 0))[0].copy()
+        return self._value_function(riccati=False).equality_multiplier(t).copy()   # (the multipliers alone)
 
     def getStateInequalityConstraintValue(self, name, t, x):
         # the reference looks `name` up among the STATE-ONLY constraints, of which the OCP has none

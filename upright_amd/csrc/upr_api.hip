@@ -307,6 +307,11 @@ struct upr_batch {
     int vf_state = 0;        // 0: no update yet; 1: current; 2: stale (the plan or the observation changed since)
     double vf_ms = 0.0;      // device time of the last cost-to-go launch
     hipEvent_t vf_ev[2] = {nullptr, nullptr};
+    double* vf_nu = nullptr;   // [B][N][ne] equality multipliers of that QP (the cost-to-go kernel's copy: upr_batch_equality_lagrangian)
+    // tracked mode (upr_batch_track_value_function): the advance hands its own last QP to the cost-to-go kernel in-stream.
+    // vf_tracked: the current cost-to-go came from an advance -- it belongs to the solve and outlives upr_batch_set_observation
+    bool vf_track = false, vf_tracked = false;
+    bool vf_ms_pending = false;   // events of a tracked launch on a timed handle recorded, vf_ms not read back yet
     std::string ls_name;   // the line-search kernel instantiation of the handle's last line-search launch (upr_batch_ls_kernel_name)
     int ls_form[5] = {0, 0, 0, 0, -1};   // (NFM, NBM, EXACT, OBS, STAGE) of that launch; STAGE -1: no line search launched yet
     std::string lin_name;   // the linearisation kernel instantiation of the handle's last linearisation launch (upr_batch_lin_kernel_name)
@@ -748,6 +753,30 @@ struct KernelTimer {
     void stop() { if (on) (void)hipEventRecord(h->ev_pool[idx + 1], h->stream); }
 };
 
+// ---- value function of the last QP: buffers, launch arguments, working set (upr_value.h)
+int vf_alloc(upr_batch* h) {
+    if (h->vf_P) return 0;
+    const size_t B = (size_t)h->B, n1 = (size_t)h->d.N + 1, nx = (size_t)h->d.nx;
+    if (dev_alloc(&h->vf_P, B * n1 * nx * nx) || dev_alloc(&h->vf_p, B * n1 * nx) || dev_alloc(&h->vf_J, B * n1) || dev_alloc(&h->vf_X, B * n1 * nx) || dev_alloc(&h->vf_t0, B) ||
+        dev_alloc(&h->vf_nu, B * (size_t)h->d.N * (size_t)h->d.ne)) return 1;
+    UPR_HIP(hipEventCreate(&h->vf_ev[0])); UPR_HIP(hipEventCreate(&h->vf_ev[1]));
+    return 0;
+}
+// the cost-to-go kernel on the QP that was launched last (records in lin, step in ws, its point in the export buffer or the workspace)
+upr_vf_args make_vf_args(upr_batch* h) {
+    upr_vf_args A;
+    A.P = h->dP; A.d = h->d; A.xs = h->xs; A.us = h->us; A.lin = h->lin; A.Df = h->Df; A.ws = h->ws;
+    const upr_qp_sel& q = h->qp;
+    A.mult = q.exported ? h->kkt : h->ws; A.mult_stride = q.stride;
+    A.o_pi = q.o_pi; A.o_nu = q.o_nu; A.o_lam = q.o_lam; A.o_t = q.o_t; A.o_sig = q.o_sig; A.o_tau = q.o_tau; A.o_gam = q.o_gam;
+    A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X; A.nu_out = h->vf_nu;
+    return A;
+}
+size_t vf_lds_bytes(const upr_batch* h) { return (size_t)upr_vf_lds_layout(h->d).total * sizeof(double); }
+// The dynamic-LDS limit of a kernel is an attribute of the FUNCTION, for the whole process: always the ceiling the callers accept
+// (160 KiB), never one handle's working set -- a smaller handle must not lower it under a larger one's in-stream launch or graph node
+hipError_t vf_raise_lds_limit() { return hipFuncSetAttribute((const void*)upr_value_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
+
 // Longest-first dispatch of the QP launch.  One workgroup solves one instance and a launch of B instances runs on
 // 2 x 256 workgroup slots, so its duration is set by the slot that draws the largest SUM of IPM iteration counts: with
 // the headline's 10..13 iterations per instance, arrival order gives 25 on some slot against a mean of 22.7.  The
@@ -776,7 +805,19 @@ int advance_impl(upr_batch* h) {
             // the production kernel writes the feedback gains of the advance's LAST QP itself (no gather kernel afterwards)
             if (h->fb && h->qp.fb_fused && it == sqp_iters - 1) Q.fb = h->fb;
             if (h->order_on && h->order_valid) Q.order = h->order;
+            // tracked value function: the advance's LAST QP exports its multipliers (exit-only code of the kernel, behind its step)
+            if (h->vf_track && it == sqp_iters - 1 && h->qp.exported) { Q.kkt = h->kkt; Q.kkt_stride = h->qp.stride; }
             KernelTimer T(h, 1); if (launch_qp(h, Q)) return 1; T.stop();
+        }
+        if (h->vf_track && it == sqp_iters - 1) {
+            // ... and the cost-to-go kernel reads that QP before the line search moves xs / us off its linearisation point
+            const bool timed = h->timing != 0;   // (a timed handle never captures a tick graph: no event nodes in it)
+            if (timed) UPR_HIP(hipEventRecord(h->vf_ev[0], h->stream));
+            hipLaunchKernelGGL(upr_value_kernel, dim3(h->B), dim3(UPR_VF_NT), vf_lds_bytes(h), h->stream, make_vf_args(h));
+            UPR_HIP(hipGetLastError());
+            if (timed) { UPR_HIP(hipEventRecord(h->vf_ev[1], h->stream)); h->vf_ms_pending = true; }
+            UPR_HIP(hipMemcpyAsync(h->vf_t0, h->t0, sizeof(double) * h->B, hipMemcpyDeviceToDevice, h->stream));
+            h->vf_state = 1; h->vf_tracked = true;
         }
         upr_ls_args L;
         L.P = h->dP; L.d = d; L.xs = h->xs; L.us = h->us; L.x0 = h->x0; L.t0 = h->t0; L.body_params = h->body_params;
@@ -937,7 +978,7 @@ void upr_batch_destroy(upr_batch* h) {
     if (h->pflag) hipFree(h->pflag);
     hipFree(h->xs_prev); hipFree(h->us_prev); hipFree(h->tprev); hipFree(h->lin); hipFree(h->Df); hipFree(h->ws); hipFree(h->stats);
     hipFree(h->done); hipFree(h->order); hipFree(h->iter_key); if (h->pin) (void)hipHostFree(h->pin); if (h->tick_exec) (void)hipGraphExecDestroy(h->tick_exec); hipFree(h->prof); hipFree(h->kkt);
-    hipFree(h->vf_P); hipFree(h->vf_p); hipFree(h->vf_J); hipFree(h->vf_X); hipFree(h->vf_t0);
+    hipFree(h->vf_P); hipFree(h->vf_p); hipFree(h->vf_J); hipFree(h->vf_X); hipFree(h->vf_t0); hipFree(h->vf_nu);
     for (hipEvent_t e : h->vf_ev) if (e) (void)hipEventDestroy(e);
     hipFree(h->ev_t); hipFree(h->ev_xo); hipFree(h->ev_x) /* (ev_u: same block) */;
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
@@ -972,7 +1013,7 @@ int upr_batch_set_target_orientations(upr_batch* h, const double* way_q) {
 
 static int set_observation_core(upr_batch* h, const double* t, int t_stride, const double* x) {
     UPR_ENTER(h);
-    if (h->vf_state) h->vf_state = 2;
+    if (h->vf_state && !h->vf_tracked) h->vf_state = 2;   // (a tracked cost-to-go belongs to the solve: valid until the next advance)
     std::vector<double> tt(h->B);
     for (int b = 0; b < h->B; ++b) tt[b] = t[(size_t)b * (t_stride ? 1 : 0)];
     UPR_HIP(hipMemcpyAsync(h->t0, tt.data(), sizeof(double) * h->B, hipMemcpyHostToDevice, h->stream));
@@ -1260,7 +1301,6 @@ static int qp_step_core(upr_batch* h, double* dxs, double* dus) {
  * [x lower][x upper][u lower][u upper][friction rows][collision / projectile rows]; *ni_out = ni.  Any pointer may be NULL. */
 int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double* nu, double* yN, double* lam, int* ni_out) {
     UPR_ENTER(h);
-    if (h->P.n_dyn) return fail("upr_batch_qp_kkt: not available with a dynamic obstacle (interface states)");
     const upr_dims& d = h->d;
     if (ni_out) *ni_out = d.ni_stage;
     const upr_qp_sel& sel = h->qp;   // (where the selected kernel left the primal-dual point: the export buffer or the workspace)
@@ -1272,7 +1312,12 @@ int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double*
     const int n1 = d.N + 1;
     for (int b = 0; b < h->B; ++b) {
         const double* w = ws.data() + (size_t)b * d.ws_stride;
-        if (dxs) std::memcpy(dxs + (size_t)b * n1 * d.nx, w + d.ws_dx, sizeof(double) * n1 * d.nx);
+        if (dxs && !h->P.n_dyn) std::memcpy(dxs + (size_t)b * n1 * d.nx, w + d.ws_dx, sizeof(double) * n1 * d.nx);
+        else if (dxs) for (int k = 0; k < n1; ++k) {   // interface width: the obstacle is data of the QP, its step is zero (upr_batch_qp_step)
+            double* o = dxs + ((size_t)b * n1 + k) * h->nxf;
+            std::memcpy(o, w + d.ws_dx + (size_t)k * d.nx, sizeof(double) * d.nx);
+            for (int c = d.nx; c < h->nxf; ++c) o[c] = 0.0;
+        }
         if (dus) std::memcpy(dus + (size_t)b * d.N * d.nu, w + d.ws_du, sizeof(double) * d.N * d.nu);
         const size_t nsl = (size_t)n1 * d.ni_stage;
         const double* m = (sel.exported ? kk.data() : ws.data()) + (size_t)b * sel.stride;
@@ -1326,19 +1371,15 @@ int upr_batch_qp_slack_pairs(upr_batch* h, double* sigma, double* tau, double* g
 }
 
 /* ---- value function of the last QP, batched (upr_value.h) ---- */
-int upr_batch_value_function_update(upr_batch* h) {
+int upr_batch_value_function_update_interface(upr_batch* h) {
     UPR_ENTER(h);
-    if (h->P.n_dyn) return fail("upr_batch_value_function_update: not available with a dynamic obstacle (interface states)");
     if (!h->has_prev && !h->guess_set) return fail("upr_batch_value_function_update: no plan on this handle yet (advance or set a guess first)");
     const upr_dims& d = h->d;
-    const size_t B = (size_t)h->B, n1 = (size_t)d.N + 1, nx = (size_t)d.nx;
-    const size_t lds = (size_t)upr_vf_lds_layout(d).total * sizeof(double);
+    const size_t B = (size_t)h->B;
+    const size_t lds = vf_lds_bytes(h);
     if (lds > 160 * 1024) return fail("upr_batch_value_function_update: working set exceeds 160 KiB of LDS");
-    if (!h->vf_P) {
-        if (dev_alloc(&h->vf_P, B * n1 * nx * nx) || dev_alloc(&h->vf_p, B * n1 * nx) || dev_alloc(&h->vf_J, B * n1) || dev_alloc(&h->vf_X, B * n1 * nx) || dev_alloc(&h->vf_t0, B)) return 1;
-        UPR_HIP(hipEventCreate(&h->vf_ev[0])); UPR_HIP(hipEventCreate(&h->vf_ev[1]));
-    }
-    h->vf_state = 0;
+    if (vf_alloc(h)) return 1;
+    h->vf_state = 0; h->vf_tracked = false; h->vf_ms_pending = false;
     // statistics and dispatch keys of the solve are put back behind the query's QP (what upr_batch_hold_stats does, on a copy of
     // its own: a caller may hold one across this call)
     const size_t ns = sizeof(double) * B * UPR_NSTATS, nk = (B + 3) & ~(size_t)3;
@@ -1347,13 +1388,8 @@ int upr_batch_value_function_update(upr_batch* h) {
     UPR_HIP(hipMemcpy(st.data(), h->stats, ns, hipMemcpyDeviceToHost));
     UPR_HIP(hipMemcpy(keys.data(), h->iter_key, nk, hipMemcpyDeviceToHost));
     if (kkt_launch(h)) return 1;
-    upr_vf_args A;
-    A.P = h->dP; A.d = d; A.xs = h->xs; A.us = h->us; A.lin = h->lin; A.Df = h->Df; A.ws = h->ws;
-    const upr_qp_sel& q = h->qp;
-    A.mult = q.exported ? h->kkt : h->ws; A.mult_stride = q.stride;
-    A.o_pi = q.o_pi; A.o_nu = q.o_nu; A.o_lam = q.o_lam; A.o_t = q.o_t; A.o_sig = q.o_sig; A.o_tau = q.o_tau; A.o_gam = q.o_gam;
-    A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X;
-    if (lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)upr_value_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const upr_vf_args A = make_vf_args(h);
+    if (lds > 64 * 1024) UPR_HIP(vf_raise_lds_limit());
     UPR_HIP(hipEventRecord(h->vf_ev[0], h->stream));
     hipLaunchKernelGGL(upr_value_kernel, dim3(h->B), dim3(UPR_VF_NT), lds, h->stream, A);
     UPR_HIP(hipGetLastError());
@@ -1369,11 +1405,40 @@ int upr_batch_value_function_update(upr_batch* h) {
     return 0;
 }
 
+/* The entry of before: robot-state shapes in every query that follows, so a handle with a dynamic obstacle (interface states) is
+ * refused here -- upr_batch_value_function_update_interface is the same update for such a handle. */
+int upr_batch_value_function_update(upr_batch* h) {
+    UPR_ENTER(h);
+    if (h->P.n_dyn) return fail("upr_batch_value_function_update: not available with a dynamic obstacle (interface states): upr_batch_value_function_update_interface takes such a handle");
+    return upr_batch_value_function_update_interface(h);
+}
+
 static int vf_ready(const upr_batch* h, const char* who) {
     if (h->vf_state == 0) return fail(std::string(who) + ": no upr_batch_value_function_update on this handle yet");
     if (h->vf_state == 2) return fail(std::string(who) + ": the cost-to-go is stale (the plan or the observation changed since upr_batch_value_function_update)");
     return 0;
 }
+
+/* Tracked mode: every advance (and tick) with at least one SQP iteration hands its own last QP to the cost-to-go kernel, in-stream
+ * between that QP launch and its line search.  Never called inside an advance (between upr_batch_advance_async and upr_batch_sync). */
+int upr_batch_track_value_function(upr_batch* h, int on) {
+    UPR_ENTER(h);
+    if (!on) {
+        if (h->vf_track && h->vf_state) h->vf_state = 2;   // (what an advance tracked is dropped with the mode)
+        h->vf_track = false; h->vf_tracked = false;
+        return 0;
+    }
+    if (h->vf_track) return 0;
+    const size_t lds = vf_lds_bytes(h);
+    if (lds > 160 * 1024) return fail("upr_batch_track_value_function: working set exceeds 160 KiB of LDS");
+    if (vf_alloc(h)) return 1;
+    if (h->qp.exported && !h->kkt && dev_alloc(&h->kkt, (size_t)h->B * h->qp.stride)) return 1;
+    if (lds > 64 * 1024) UPR_HIP(vf_raise_lds_limit());
+    h->vf_track = true;
+    return 0;
+}
+
+static void narrow_states(const upr_batch* h, const double* xf, size_t n, std::vector<double>& xr);
 
 int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double* t, const double* x, double* V, double* dVdx) {
     UPR_ENTER(h);
@@ -1386,7 +1451,12 @@ int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double*
     if (dinst.alloc(n) || dt_.alloc(n) || dx.alloc((size_t)n * d.nx) || dV.alloc(n) || dg.alloc((size_t)n * d.nx)) return 1;
     UPR_HIP(hipMemcpy(dinst, inst, sizeof(int) * n, hipMemcpyHostToDevice));
     UPR_HIP(hipMemcpy(dt_, t, sizeof(double) * n, hipMemcpyHostToDevice));
-    UPR_HIP(hipMemcpy(dx, x, sizeof(double) * n * d.nx, hipMemcpyHostToDevice));
+    if (!h->P.n_dyn) UPR_HIP(hipMemcpy(dx, x, sizeof(double) * n * d.nx, hipMemcpyHostToDevice));
+    else {   // interface states: the robot block is what the expansion is in
+        std::vector<double> xr;
+        narrow_states(h, x, (size_t)n, xr);
+        UPR_HIP(hipMemcpy(dx, xr.data(), sizeof(double) * n * d.nx, hipMemcpyHostToDevice));
+    }
     upr_vfq_args A;
     A.d = d; A.dt = h->P.dt; A.n = n; A.inst = dinst; A.t = dt_; A.x = dx; A.t0 = h->vf_t0;
     A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X; A.V = dV; A.dV = dg;
@@ -1394,7 +1464,38 @@ int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double*
     UPR_HIP(hipGetLastError());
     UPR_HIP(hipStreamSynchronize(h->stream));
     if (V) UPR_HIP(hipMemcpy(V, dV, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (dVdx) UPR_HIP(hipMemcpy(dVdx, dg, sizeof(double) * n * d.nx, hipMemcpyDeviceToHost));
+    if (dVdx && !h->P.n_dyn) UPR_HIP(hipMemcpy(dVdx, dg, sizeof(double) * n * d.nx, hipMemcpyDeviceToHost));
+    else if (dVdx) {   // the obstacle is data of the QP, not a state of its Riccati recursion: zero block
+        std::vector<double> gr((size_t)n * d.nx);
+        UPR_HIP(hipMemcpy(gr.data(), dg, sizeof(double) * gr.size(), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) {
+            std::memcpy(dVdx + (size_t)i * h->nxf, gr.data() + (size_t)i * d.nx, sizeof(double) * d.nx);
+            for (int c = d.nx; c < h->nxf; ++c) dVdx[(size_t)i * h->nxf + c] = 0.0;
+        }
+    }
+    return 0;
+}
+
+/* nu(t) of the QP the cost-to-go belongs to, nu_out[n][ne]: multipliers of the object-dynamics rows, piecewise linear between the knots */
+int upr_batch_equality_lagrangian(upr_batch* h, int n, const int* inst, const double* t, double* nu_out) {
+    UPR_ENTER(h);
+    if (vf_ready(h, "upr_batch_equality_lagrangian")) return 1;
+    if (n <= 0) return 0;
+    if (!inst || !t || !nu_out) return fail("upr_batch_equality_lagrangian: null argument");
+    const upr_dims& d = h->d;
+    for (int i = 0; i < n; ++i) if (inst[i] < 0 || inst[i] >= h->B) return fail("instance index out of range");
+    DevBuf<int> dinst; DevBuf<double> dt_, dn;
+    if (dinst.alloc(n) || dt_.alloc(n) || dn.alloc((size_t)n * d.ne)) return 1;
+    UPR_HIP(hipMemcpy(dinst, inst, sizeof(int) * n, hipMemcpyHostToDevice));
+    UPR_HIP(hipMemcpy(dt_, t, sizeof(double) * n, hipMemcpyHostToDevice));
+    upr_vfq_args A;
+    A.d = d; A.dt = h->P.dt; A.n = n; A.inst = dinst; A.t = dt_; A.x = nullptr; A.t0 = h->vf_t0;
+    A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X; A.V = nullptr; A.dV = nullptr;
+    A.nu = h->vf_nu; A.nu_q = dn;
+    hipLaunchKernelGGL(upr_value_query_kernel, dim3(n), dim3(64), 0, h->stream, A);
+    UPR_HIP(hipGetLastError());
+    UPR_HIP(hipStreamSynchronize(h->stream));
+    UPR_HIP(hipMemcpy(nu_out, dn, sizeof(double) * n * d.ne, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1410,7 +1511,15 @@ int upr_batch_get_cost_to_go(upr_batch* h, double* Pk, double* pk, double* J, do
     return 0;
 }
 
-double upr_batch_value_function_ms(const upr_batch* h) { return h ? h->vf_ms : 0.0; }
+double upr_batch_value_function_ms(upr_batch* h) {
+    if (!h) return 0.0;
+    if (h->vf_ms_pending) {   // a tracked launch on a timed handle: its events are read here, after the advance (waits for the launch)
+        float ms = 0.0f;
+        if (hipEventSynchronize(h->vf_ev[1]) == hipSuccess && hipEventElapsedTime(&ms, h->vf_ev[0], h->vf_ev[1]) == hipSuccess) h->vf_ms = ms;
+        h->vf_ms_pending = false;
+    }
+    return h->vf_ms;
+}
 
 int upr_batch_device_ptrs(upr_batch* h, void** xs, void** us) {
     UPR_ENTER(h);
@@ -1629,12 +1738,14 @@ int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x,
     for (unsigned long long v : {(unsigned long long)h->has_prev, (unsigned long long)h->guess_set, (unsigned long long)sqp_now, (unsigned long long)(h->order_on && h->order_valid),
                                  (unsigned long long)(h->fb != nullptr), (unsigned long long)h->qp.fb_fused, (unsigned long long)h->timing, (unsigned long long)(stats_out != nullptr),
                                  (unsigned long long)h->qp.structure, (unsigned long long)h->qp.source, (unsigned long long)h->qp.nt, (unsigned long long)(uintptr_t)h->pin,
-                                 (unsigned long long)(uintptr_t)h->prof /* (passed BY VALUE in upr_qp_args: a graph captured before upr_batch_qp_profile allocated it would keep nullptr) */}) { sig ^= v; sig *= 1099511628211ull; }
+                                 (unsigned long long)(uintptr_t)h->prof /* (passed BY VALUE in upr_qp_args: a graph captured before upr_batch_qp_profile allocated it would keep nullptr) */,
+                                 (unsigned long long)h->vf_track /* (one more kernel node and one more copy node in the period) */}) { sig ^= v; sig *= 1099511628211ull; }
     const bool steady = h->tick_graph_on && !h->timing && h->has_prev && !h->guess_set && h->sqp_iters_next == 0 && (!h->order_on || h->order_valid);
     if (steady && h->tick_exec && sig == h->tick_sig) {
         UPR_HIP(hipGraphLaunch(h->tick_exec, h->stream));
         // (what advance_impl does on the host besides enqueueing)
         h->hdyn_prev = h->hdyn0;
+        if (h->vf_track && sqp_now > 0) { h->vf_state = 1; h->vf_tracked = true; }
         ++h->tick_replays;
     } else {
         if (h->tick_exec && sig != h->tick_sig) { (void)hipGraphExecDestroy(h->tick_exec); h->tick_exec = nullptr; h->tick_steady = 0; }

@@ -37,6 +37,9 @@ struct upr_vf_args {
     double* pk;          // [B][N+1][nx]
     double* J;           // [B][N+1]
     double* X;           // [B][N+1][nx]
+    // [B][N][ne] or NULL: the QP's multipliers nu of the object-dynamics rows, copied out of `mult` with the other per-knot stores
+    // (the export buffer and the workspace are overwritten by the next QP; this copy is what the nu(t) query reads)
+    double* nu_out = nullptr;
 };
 
 // LDS layout (doubles)
@@ -101,6 +104,7 @@ static inline UPR_HD void upr_vf_instance(const upr_ctx& ctx, const upr_vf_args&
     // ---- expansion points, gradients of the knots k >= 1 (the costates), cost of every knot (a lane per knot)
     if (ctx.tid == 0) L[o.flag] = 0.0;
     UPR_FOR(e, (N + 1) * nx) { X[e] = xs[e] + dx[e]; if (e >= nx) pk[e] = M[A.o_pi + e]; }
+    if (A.nu_out) { double* nuo = A.nu_out + (size_t)b * N * ne; UPR_FOR(e, N * ne) nuo[e] = M[A.o_nu + e]; }
     UPR_FOR(k, N + 1) {
         const double* rec = lin + (size_t)k * d.lin_stride;
         const double* dxk = dx + k * nx;
@@ -236,7 +240,8 @@ static inline UPR_HD void upr_vf_instance(const upr_ctx& ctx, const upr_vf_args&
 }
 
 // ---- query: V and dV/dx at points (inst, t, x), the expansions of the two neighbouring knots interpolated linearly in t
-// (value_function.ValueFunction._seg / value / gradient)
+// (value_function.ValueFunction._seg / value / gradient), and the equality multipliers nu(t) of the same segment
+// (ValueFunction.equality_multiplier: piecewise linear, the last knot carries none, so nu[min(j + 1, N - 1)] is the right neighbour)
 struct upr_vfq_args {
     upr_dims d;
     double dt;
@@ -248,6 +253,9 @@ struct upr_vfq_args {
     const double *Pk, *pk, *J, *X;
     double* V;           // [n]
     double* dV;          // [n][nx]
+    const double* nu = nullptr;   // [B][N][ne] (upr_vf_args::nu_out) or NULL: no multiplier query
+    double* nu_q = nullptr;       // [n][ne]
+    // (x == NULL: the multiplier query alone -- V and dV are not written)
 };
 static inline UPR_HD void upr_vf_query_point(const upr_ctx& ctx, const upr_vfq_args& A, int p, double* L) {
     const int nx = A.d.nx, N = A.d.N, b = A.inst[p];
@@ -255,6 +263,12 @@ static inline UPR_HD void upr_vf_query_point(const upr_ctx& ctx, const upr_vfq_a
     s = s > 0.0 ? s : 0.0; s = s < (double)N ? s : (double)N;
     int j = (int)s; if (j > N - 1) j = N - 1;
     const double a = s - j;
+    if (A.nu) {   // (ne reaches 48 on the robust shape, 64 lanes a point: a loop over the rows, not a lane per row)
+        const int ne = A.d.ne, jr = (j + 1 < N - 1) ? j + 1 : N - 1;
+        const double* n0 = A.nu + ((size_t)b * N + j) * ne; const double* n1 = A.nu + ((size_t)b * N + jr) * ne;
+        UPR_FOR(r, ne) A.nu_q[(size_t)p * ne + r] = (1.0 - a) * n0[r] + a * n1[r];
+    }
+    if (!A.x) return;
     const double* xp = A.x + (size_t)p * nx;
     UPR_FOR(i, nx) {
         for (int kk = 0; kk < 2; ++kk) {

@@ -204,7 +204,7 @@ class BatchMPC:
         P = self.problem
         ni = C.c_int(0)
         nin = 2 * self.nx + 2 * self.nu + (5 * P.nc if P.nf == 3 else 0) + P.n_state_rows
-        out = dict(dx=np.zeros((self.B, self.N + 1, self.nx)), du=np.zeros((self.B, self.N, self.nu)),
+        out = dict(dx=np.zeros((self.B, self.N + 1, self.nxf)), du=np.zeros((self.B, self.N, self.nu)),   # (dx: interface width, zero obstacle block)
                    pi=np.zeros((self.B, self.N + 1, self.nx)), nu=np.zeros((self.B, self.N, self.ne)),
                    yN=np.zeros((self.B, 3 + 2 * P.nq if P.terminal_constraint else 0)), lam=np.zeros((self.B, self.N + 1, nin)))
         check(self._lib.upr_batch_qp_kkt(self._h, ptr(out["dx"]), ptr(out["du"]), ptr(out["pi"]), ptr(out["nu"]),
@@ -223,26 +223,51 @@ class BatchMPC:
         return sig, tau, gam
 
     # -- value function of the last QP, batched on the device --------------------------------------------
-    def value_function_update(self):
+    def value_function_update(self, interface_states=False):
         """Linearise at the current plan, solve one QP there and run the cost-to-go kernel for every instance; statistics and
-        dispatch keys of the last advance are left as they were (upr_batch_value_function_update)."""
-        check(self._lib.upr_batch_value_function_update(self._h))
+        dispatch keys of the last advance are left as they were (upr_batch_value_function_update).  A handle with a dynamic obstacle
+        is refused unless interface_states is set: the caller then takes value_function's interface-state convention
+        (upr_batch_value_function_update_interface)."""
+        if interface_states:
+            check(self._lib.upr_batch_value_function_update_interface(self._h))
+        else:
+            check(self._lib.upr_batch_value_function_update(self._h))
+
+    def track_value_function(self, on=True):
+        """Tracked mode: every advance() / tick() hands its own last QP to the cost-to-go kernel in-stream, so that value_function,
+        cost_to_go and equality_lagrangian answer for the QP the solve ran last (ocs2's expansion point) without an update; the result
+        stays valid across set_observation until the next advance (upr_batch_track_value_function)."""
+        check(self._lib.upr_batch_track_value_function(self._h, 1 if on else 0))
 
     def value_function(self, t, x, inst=None):
-        """V (n,) and dV/dx (n, nx) at n points: states x (n, nx), times t (scalar or (n,)), instance of each point (default:
-        point i belongs to instance i when n == B, else instance 0)."""
-        x = cont(x).reshape(-1, self.nx)
+        """V (n,) and dV/dx (n, nxf) at n points: interface states x (n, nxf), times t (scalar or (n,)), instance of each point
+        (default: point i belongs to instance i when n == B, else instance 0).  The obstacle block of dV/dx is zero."""
+        x = cont(x).reshape(-1, self.nxf)
         n = x.shape[0]
         t = cont(np.broadcast_to(np.asarray(t, dtype=np.float64), (n,)))
         if inst is None:
             inst = np.arange(n) if n == self.B else np.zeros(n)
         inst = cont(np.broadcast_to(np.asarray(inst), (n,)), dtype=np.int32)
-        V, g = np.zeros(n), np.zeros((n, self.nx))
+        V, g = np.zeros(n), np.zeros((n, self.nxf))
         check(self._lib.upr_batch_value_function(self._h, n, iptr(inst), ptr(t), ptr(x), ptr(V), ptr(g)))
         return V, g
 
+    def equality_lagrangian(self, t, inst=None):
+        """nu(t) (n, ne): multipliers of the object-dynamics rows of the QP the cost-to-go belongs to at times t (scalar: one per
+        instance, or (n,)), piecewise linear between the knots (upr_batch_equality_lagrangian)."""
+        t = np.asarray(t, dtype=np.float64)
+        n = self.B if t.ndim == 0 else t.shape[0]
+        t = cont(np.broadcast_to(t, (n,)))
+        if inst is None:
+            inst = np.arange(n) if n == self.B else np.zeros(n)
+        inst = cont(np.broadcast_to(np.asarray(inst), (n,)), dtype=np.int32)
+        nu = np.zeros((n, self.ne))
+        check(self._lib.upr_batch_equality_lagrangian(self._h, n, iptr(inst), ptr(t), ptr(nu)))
+        return nu
+
     def cost_to_go(self):
-        """dict(Pk (B, N + 1, nx, nx), pk (B, N + 1, nx), J (B, N + 1), X (B, N + 1, nx)) of the last value_function_update()."""
+        """dict(Pk (B, N + 1, nx, nx), pk (B, N + 1, nx), J (B, N + 1), X (B, N + 1, nx)) of the last value_function_update() or, in tracked mode,
+        of the last advance() / tick(): robot-block shapes also with dynamic obstacles."""
         out = dict(Pk=np.zeros((self.B, self.N + 1, self.nx, self.nx)), pk=np.zeros((self.B, self.N + 1, self.nx)),
                    J=np.zeros((self.B, self.N + 1)), X=np.zeros((self.B, self.N + 1, self.nx)))
         check(self._lib.upr_batch_get_cost_to_go(self._h, ptr(out["Pk"]), ptr(out["pk"]), ptr(out["J"]), ptr(out["X"])))

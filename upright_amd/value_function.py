@@ -17,8 +17,8 @@ object-dynamics rows, multipliers lam and slacks t of every inequality row.  Fro
     recursion        P_k = Hxx + A' P+ A - G' M^-1 G,   M = [[Huu + B' P+ B, D'], [D, -rho I]],   G = [B' P+ A; C]
 
 (a softened INEQUALITY row is factored with w0 (Z + w_s) / (Z + w0 + w_s), w0 = lam / t, w_s = gam / tau of the slack's own barrier
-pair: `riccati_value_function(..., pairs=BatchMPC.qp_slack_pairs())` covers it; control_bindings.ControllerInterface, which passes no
-pairs, keeps refusing the queries for such problems) and the gradient of the cost-to-go at the plan's own state is the costate pi_k.
+pair: `riccati_value_function(..., pairs=BatchMPC.qp_slack_pairs())` covers it; control_bindings.ControllerInterface answers
+such problems, and those with a dynamic obstacle, from the device path below) and the gradient of the cost-to-go at the plan's own state is the costate pi_k.
 The same recursion runs for the whole batch on the device: upright_amd/csrc/upr_value.h behind BatchMPC.value_function_update(), for
 which this module is the specification.  Around the plan
     V(t, x) ~ J(t) + pi(t)' (x - x*(t)) + 1/2 (x - x*(t))' P(t) (x - x*(t)),     dV/dx = pi(t) + P(t) (x - x*(t))
