@@ -339,6 +339,36 @@ int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double*
 int upr_batch_get_cost_to_go(upr_batch* h, double* Pk, double* pk, double* J, double* X);
 double upr_batch_value_function_ms(upr_batch* h);
 
+/* ------------------------------------------------------------------------------------------------
+ * Balance check under inertial-parameter scenarios: does a state stay balanced when the true parameters are not the ones it was
+ * planned with?  Replaces the off-line test of upright_robust/scripts/process_sim_runs.py:87-270 (is the wrench an object needs
+ * inside the contact wrench cone of upright_robust/src/upright_robust/modelling.py:106-132), batched on the device
+ * (upright_amd/csrc/upr_balance.h: a state kernel and a Lawson-Hanson projection in fp64 -- a lane per job with the passive system
+ * in registers for one-body arrangements, a wave per job with the passive system in LDS for every other shape).
+ *   For a robot state x = [q, v, a], parameters theta[nb][10] (the layout of body_params) and the handle's arrangement:
+ *       rho(x; theta) = min over z >= 0 of | b + A z |_2,   b = g(x, f = 0; theta),   A = dg/df(theta) S,
+ *   g the object-dynamics residual exactly as the linearisation records it (per body divided by its mass, the whole vector by
+ *   sqrt(6 nb)), S the generators of the friction pyramids, contact by contact in the order n + mu s0, n + mu s1, n - mu s0,
+ *   n - mu s1 (nf = 3: ncol = 4 nc) or the normal alone (nf = 1: ncol = nc); contact forces are f = S z.  rho is the distance, in the
+ *   units of the constraint the controller enforces, from the needed wrench to the contact wrench cone: rho = 0 if and only if
+ *   balancing forces exist.  The force bounds u_lb / u_ub are NOT part of it.  Levers and 1 / m in A follow theta, not the
+ *   handle's own parameters.  rho is unique, z is not.
+ *   Stopping rule (UPR_BAL_TOL of upr_balance.h, 1e-14): a column enters only while -a_j' r > tol |a_j| max(|b|, 1); iteration cap
+ *   3 ncol least-squares solves -- a job that reaches it reports exactly that count in iters.
+ *   upr_batch_balance_points  n states x[n][3 nq] (robot states, also with dynamic obstacles) times n_scen scenarios:
+ *       params[n_scen][nb][10] shared by all points (per_point == 0) or params[n][n_scen][nb][10] (per_point == 1);
+ *       rho[n][n_scen], z[n][n_scen][ncol] or NULL, iters[n][n_scen] or NULL.  Host pointers.
+ *   upr_batch_balance_plan  the knots of the handle's current plan where they lie on the device (no host copy of xs), enqueued on
+ *       the handle's stream behind whatever is in flight, one synchronisation at the end: rho[B][N+1][n_scen], iters likewise or
+ *       NULL.  params == NULL with n_scen == 1: each instance against its own body_params (the nominal check); else
+ *       params[n_scen][nb][10], or params[B][n_scen][nb][10] with per_instance != 0.
+ *   Both leave the plan, statistics, dispatch keys, warm start, value-function validity and tick graph exactly as they were. */
+int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point,
+                             double* rho, double* z, int* iters);
+int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double* rho, int* iters);
+/* device time (ms) of the two kernel launches of the last balance check on the handle, HIP events around them (copies excluded) */
+double upr_batch_balance_ms(upr_batch* h);
+
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):
  * xs (B*(N+1)*nx doubles) and us (B*N*nu doubles) */
 int upr_batch_device_ptrs(upr_batch* h, void** xs, void** us);

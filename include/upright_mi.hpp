@@ -96,6 +96,24 @@ class ControllerInterface {
         V.assign((size_t)n, 0.0); dVdx.assign((size_t)n * nx_, 0.0);
         check(upr_batch_value_function(h_, n, inst.data(), t.data(), x.data(), V.data(), dVdx.data()));
     }
+    // balance check of the current plan under n_scen inertial-parameter scenarios (upr_batch_balance_plan): rho[B][N+1][n_scen], the
+    // distance of every knot's needed wrench to the contact wrench cone; params[n_scen][nb][10], or [B][n_scen][nb][10] with
+    // per_instance; empty params: every instance against its own body parameters (n_scen = 1)
+    std::vector<double> balance_check_plan(const std::vector<double>& params = {}, int n_scen = 1, bool per_instance = false) {
+        if (!params.empty() && (int)params.size() != (per_instance ? B_ : 1) * n_scen * P_.nb * 10) throw std::runtime_error("params must hold [B][n_scen][nb][10] or [n_scen][nb][10] values");
+        if (params.empty()) n_scen = 1;
+        std::vector<double> rho((size_t)B_ * (P_.N + 1) * n_scen);
+        check(upr_batch_balance_plan(h_, n_scen, params.empty() ? nullptr : params.data(), per_instance ? 1 : 0, rho.data(), nullptr));
+        return rho;
+    }
+    // the same at n robot states x[n][nx] (upr_batch_balance_points), params[n_scen][nb][10] shared by all points: rho[n][n_scen]
+    std::vector<double> balance_check(const std::vector<double>& x, const std::vector<double>& params, int n_scen) {
+        const int n = (int)x.size() / nx_;
+        if ((int)x.size() != n * nx_ || (int)params.size() != n_scen * P_.nb * 10) throw std::runtime_error("x must hold n * nx and params n_scen * nb * 10 values");
+        std::vector<double> rho((size_t)n * n_scen);
+        check(upr_batch_balance_points(h_, n, x.data(), n_scen, params.data(), 0, rho.data(), nullptr, nullptr));
+        return rho;
+    }
     upr_batch* handle() { return h_; }
 
    private:

@@ -154,6 +154,9 @@ PROTOTYPES = [
     ("upr_batch_value_function", C.c_int, [C.c_void_p, C.c_int, ip, dp, dp, dp, dp]),
     ("upr_batch_get_cost_to_go", C.c_int, [C.c_void_p, dp, dp, dp, dp]),
     ("upr_batch_value_function_ms", C.c_double, [C.c_void_p]),
+    ("upr_batch_balance_points", C.c_int, [C.c_void_p, C.c_int, dp, C.c_int, dp, C.c_int, dp, dp, ip]),
+    ("upr_batch_balance_plan", C.c_int, [C.c_void_p, C.c_int, dp, C.c_int, dp, ip]),
+    ("upr_batch_balance_ms", C.c_double, [C.c_void_p]),
     ("upr_batch_device_ptrs", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("upr_batch_kernel_times", C.c_int, [C.c_void_p, dp, ip]),
     ("upr_batch_enable_timing", C.c_int, [C.c_void_p, C.c_int]),

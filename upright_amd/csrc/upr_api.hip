@@ -32,6 +32,7 @@
 #include "upr_qp3_launch.h"
 #include "upr_qp_select.h"
 #include "upr_value.h"
+#include "upr_balance.h"
 
 namespace {
 
@@ -312,6 +313,11 @@ struct upr_batch {
     // vf_tracked: the current cost-to-go came from an advance -- it belongs to the solve and outlives upr_batch_set_observation
     bool vf_track = false, vf_tracked = false;
     bool vf_ms_pending = false;   // events of a tracked launch on a timed handle recorded, vf_ms not read back yet
+    // balance check (upr_balance.h): HIP events around the two launches of the last call and their distance (upr_batch_balance_ms)
+    hipEvent_t bal_ev[2] = {nullptr, nullptr};
+    double bal_ms = 0.0;
+    void* bal_buf = nullptr; size_t bal_cap = 0;   // scratch of the balance-check calls, grown on demand, used for nothing else
+    bool bal_lane = true;   // one-body shapes on the lane-per-job kernel (UPR_BAL_FORM=0 at create: the wave-per-job kernel for them too; tests)
     std::string ls_name;   // the line-search kernel instantiation of the handle's last line-search launch (upr_batch_ls_kernel_name)
     int ls_form[5] = {0, 0, 0, 0, -1};   // (NFM, NBM, EXACT, OBS, STAGE) of that launch; STAGE -1: no line search launched yet
     std::string lin_name;   // the linearisation kernel instantiation of the handle's last linearisation launch (upr_batch_lin_kernel_name)
@@ -846,6 +852,75 @@ int advance_impl(upr_batch* h) {
     return 0;
 }
 
+// ---- balance check (upr_balance.h): both entry points end here.  x_host: n states [n][3 nq] to upload, or NULL with dx already on
+// the device; params_host: parameter blocks to upload ([count][nb][10]) or NULL with dparams already on the device.  Everything is
+// enqueued on the handle's stream behind whatever is in flight and the one synchronisation is the last statement.  The scratch of
+// the calls is one block on the handle that serves nothing else and only grows (bal_buf: states, kernel outputs, uploaded
+// parameters and points): a call in the steady state allocates and frees nothing.
+size_t bal_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+int balance_scratch(upr_batch* h, size_t bytes) {
+    if (bytes <= h->bal_cap) return 0;
+    if (h->bal_buf) { UPR_HIP(hipFree(h->bal_buf)); h->bal_buf = nullptr; h->bal_cap = 0; }
+    UPR_HIP(hipMalloc(&h->bal_buf, bytes));
+    h->bal_cap = bytes;
+    return 0;
+}
+int balance_check_params(const upr_batch* h, const double* params, size_t count) {
+    const int nb = h->d.nb;
+    for (size_t i = 0; i < count * nb; ++i)
+        if (!(params[10 * i] > 0) || !std::isfinite(params[10 * i])) return fail("balance check: every body of every scenario needs a positive finite mass");
+    return 0;
+}
+int balance_run(upr_batch* h, long long n, const double* x_host, const double* dx, int n_scen, const double* params_host, size_t params_count,
+                const double* dparams, int pdiv, double* rho, double* z, int* iters) {
+    const upr_dims& d = h->d;
+    const upr_bal_dims L = upr_bal_layout(d.nb, d.nc, d.nf);
+    const long long njobs = n * n_scen;
+    if (n > (1ll << 31) - 64 || njobs > (1ll << 36)) return fail("balance check: too many points");
+    const size_t o_st = 0, o_rho = o_st + bal_up(sizeof(double) * n * UPR_BAL_ST), o_z = o_rho + bal_up(sizeof(double) * njobs),
+                 o_it = o_z + (z ? bal_up(sizeof(double) * njobs * L.ncol) : 0), o_par = o_it + (iters ? bal_up(sizeof(int) * njobs) : 0),
+                 o_x = o_par + (params_host ? bal_up(sizeof(double) * params_count * d.nb * 10) : 0),
+                 total = o_x + (x_host ? bal_up(sizeof(double) * n * d.nx) : 0);
+    if (balance_scratch(h, total)) return 1;
+    char* base = (char*)h->bal_buf;
+    double* dst = (double*)(base + o_st); double* drho = (double*)(base + o_rho); double* dz = (double*)(base + o_z); int* dit = (int*)(base + o_it);
+    if (params_host) {
+        UPR_HIP(hipMemcpyAsync(base + o_par, params_host, sizeof(double) * params_count * d.nb * 10, hipMemcpyHostToDevice, h->stream));
+        dparams = (const double*)(base + o_par);
+    }
+    if (x_host) {
+        UPR_HIP(hipMemcpyAsync(base + o_x, x_host, sizeof(double) * n * d.nx, hipMemcpyHostToDevice, h->stream));
+        dx = (const double*)(base + o_x);
+    }
+    if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
+    UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
+    const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
+    if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
+    else hipLaunchKernelGGL(upr_bal_state_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
+    UPR_HIP(hipGetLastError());
+    upr_bal_args A;
+    A.P = h->dP; A.n = (int)n; A.n_scen = n_scen; A.st = dst; A.params = dparams; A.pdiv = pdiv; A.eq_scale = d.eq_scale;
+    A.rho = drho; A.z = z ? dz : nullptr; A.iters = iters ? dit : nullptr;
+    if (upr_bal_lane_form(d.nb) && h->bal_lane) {
+        hipLaunchKernelGGL(upr_bal_project1_kernel, dim3((unsigned)((njobs + 63) / 64)), dim3(64), 0, h->stream, A, L, njobs);
+    } else {
+        // jobs are dealt round robin to a grid that fills the device a few times over (a workgroup is one wave; its LDS, at most
+        // 26.4 KB, lets six of the largest shape share a CU inside the 160 KiB)
+        const long long grid = njobs < 16384 ? njobs : 16384;
+        hipLaunchKernelGGL(upr_bal_project_kernel, dim3((unsigned)grid), dim3(64), (size_t)L.total * sizeof(double), h->stream, A, L, njobs);
+    }
+    UPR_HIP(hipGetLastError());
+    UPR_HIP(hipEventRecord(h->bal_ev[1], h->stream));
+    UPR_HIP(hipMemcpyAsync(rho, drho, sizeof(double) * njobs, hipMemcpyDeviceToHost, h->stream));
+    if (z) UPR_HIP(hipMemcpyAsync(z, dz, sizeof(double) * njobs * L.ncol, hipMemcpyDeviceToHost, h->stream));
+    if (iters) UPR_HIP(hipMemcpyAsync(iters, dit, sizeof(int) * njobs, hipMemcpyDeviceToHost, h->stream));
+    UPR_HIP(hipStreamSynchronize(h->stream));
+    float ms = 0.0f;
+    UPR_HIP(hipEventElapsedTime(&ms, h->bal_ev[0], h->bal_ev[1]));
+    h->bal_ms = ms;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -927,6 +1002,7 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
     if (const char* e = getenv("UPR_LIN_MFMA")) h->use_mfma = atoi(e) != 0;
     if (const char* e = getenv("UPR_LIN2")) h->lin2 = atoi(e) != 0;
     if (const char* e = getenv("UPR_QP_ORDER")) h->order_on = atoi(e) != 0;
+    if (const char* e = getenv("UPR_BAL_FORM")) h->bal_lane = atoi(e) != 0;
     auto bad = [&]() { upr_batch_destroy(h); return (upr_batch*)nullptr; };
     if (hipStreamCreate(&h->stream) != hipSuccess) { fail("hipStreamCreate failed"); return bad(); }
     if (hipMalloc((void**)&h->dP, sizeof(upr_problem)) != hipSuccess) { fail("hipMalloc failed"); return bad(); }
@@ -980,6 +1056,8 @@ void upr_batch_destroy(upr_batch* h) {
     hipFree(h->done); hipFree(h->order); hipFree(h->iter_key); if (h->pin) (void)hipHostFree(h->pin); if (h->tick_exec) (void)hipGraphExecDestroy(h->tick_exec); hipFree(h->prof); hipFree(h->kkt);
     hipFree(h->vf_P); hipFree(h->vf_p); hipFree(h->vf_J); hipFree(h->vf_X); hipFree(h->vf_t0); hipFree(h->vf_nu);
     for (hipEvent_t e : h->vf_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->bal_ev) if (e) (void)hipEventDestroy(e);
+    hipFree(h->bal_buf);
     hipFree(h->ev_t); hipFree(h->ev_xo); hipFree(h->ev_x) /* (ev_u: same block) */;
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
@@ -1520,6 +1598,32 @@ double upr_batch_value_function_ms(upr_batch* h) {
     }
     return h->vf_ms;
 }
+
+int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double* rho, double* z, int* iters) {
+    UPR_ENTER(h);
+    if (n <= 0) return 0;
+    if (!x || !params || !rho) return fail("upr_batch_balance_points: x, params and rho must not be NULL");
+    if (n_scen < 1) return fail("upr_batch_balance_points: n_scen must be >= 1");
+    const size_t count = (size_t)(per_point ? n : 1) * n_scen;
+    if (balance_check_params(h, params, count)) return 1;
+    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, rho, z, iters);
+}
+
+int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double* rho, int* iters) {
+    UPR_ENTER(h);
+    if (!rho) return fail("upr_batch_balance_plan: rho must not be NULL");
+    const long long n = (long long)h->B * (h->d.N + 1);
+    if (!params) {   // the nominal check: every instance against its own body parameters
+        if (n_scen != 1) return fail("upr_batch_balance_plan: params == NULL needs n_scen == 1 (every instance's own body parameters)");
+        return balance_run(h, n, nullptr, h->xs, 1, nullptr, 0, h->body_params, h->d.N + 1, rho, nullptr, iters);
+    }
+    if (n_scen < 1) return fail("upr_batch_balance_plan: n_scen must be >= 1");
+    const size_t count = (size_t)(per_instance ? h->B : 1) * n_scen;
+    if (balance_check_params(h, params, count)) return 1;
+    return balance_run(h, n, nullptr, h->xs, n_scen, params, count, nullptr, per_instance ? h->d.N + 1 : 0, rho, nullptr, iters);
+}
+
+double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }
 
 int upr_batch_device_ptrs(upr_batch* h, void** xs, void** us) {
     UPR_ENTER(h);

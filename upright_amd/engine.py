@@ -277,6 +277,73 @@ class BatchMPC:
         """Device time (ms) of the last cost-to-go launch."""
         return float(self._lib.upr_batch_value_function_ms(self._h))
 
+    # -- balance check under inertial-parameter scenarios ---------------------------------------------------
+    @property
+    def balance_columns(self):
+        """Cone generators of the arrangement: four per contact (n + mu s0, n + mu s1, n - mu s0, n - mu s1) with friction, the
+        normal alone without."""
+        return self.problem.nc * (4 if self.problem.nf == 3 else 1)
+
+    def balance_check(self, x, params, want_z=False, want_iters=False):
+        """rho (n, n_scen): the distance of the wrench the bodies need at the robot states x (n, 3 nq) to the contact wrench cone of
+        the arrangement, under the inertial parameters params (n_scen, nb, 10) shared by all points or (n, n_scen, nb, 10) per
+        point -- 0 if and only if balancing forces exist (upr_batch_balance_points; the force bounds are not part of it).  With
+        want_z / want_iters the tuple (rho, z (n, n_scen, ncol), iters (n, n_scen)) restricted to what was asked for; z are the
+        multipliers of the cone generators (balance_forces turns them into contact forces).
+
+        The study's sweep (upright_robust/scripts/planning_sim_loop.py:548-559,613-616: the centre of mass at the centre, the face
+        centres and the vertices of its box, times three inertia scales = 45 scenarios) for a one-body arrangement:
+
+            th = mpc.problem.body_params                      # (1, 10): [m, m c, vech(I)]
+            h = np.array([0.02, 0.02, 0.03])                  # half extents of the CoM box
+            offs = [np.zeros(3)] + [s * h[a] * np.eye(3)[a] for a in range(3) for s in (1, -1)] + [(2 * np.array(v) - 1) * h for v in np.ndindex(2, 2, 2)]
+            params = []
+            for d in offs:
+                for k in (1.0, 0.5, 0.1):
+                    p = th.copy(); p[:, 1:4] += p[:, :1] * d; p[:, 4:] *= k
+                    params.append(p)
+            rho = mpc.balance_check_plan(np.stack(params))    # (B, N + 1, 45)
+            unsafe = (rho > 1e-6).any(axis=(1, 2))            # instances whose plan loses balance in some scenario
+        """
+        P = self.problem
+        x = cont(x).reshape(-1, self.nx)
+        n = x.shape[0]
+        params = cont(params)
+        per_point = params.ndim == 4
+        params = params.reshape((n, -1, P.nb, 10) if per_point else (-1, P.nb, 10))
+        n_scen = params.shape[1] if per_point else params.shape[0]
+        rho = np.zeros((n, n_scen))
+        z = np.zeros((n, n_scen, self.balance_columns)) if want_z else None
+        iters = np.zeros((n, n_scen), dtype=np.int32) if want_iters else None
+        check(self._lib.upr_batch_balance_points(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, ptr(rho), ptr(z), iptr(iters)))
+        out = (rho,) + ((z,) if want_z else ()) + ((iters,) if want_iters else ())
+        return out[0] if len(out) == 1 else out
+
+    def balance_check_plan(self, params=None, want_iters=False):
+        """rho (B, N + 1, n_scen) at the knots of the current plan, evaluated where they lie on the device (upr_batch_balance_plan).
+        params None: every instance against its own body parameters (n_scen = 1, the nominal check); (n_scen, nb, 10): the same
+        scenarios for every instance; (B, n_scen, nb, 10): per instance."""
+        P = self.problem
+        if params is None:
+            n_scen, per_instance, pp = 1, 0, None
+        else:
+            params = cont(params)
+            per_instance = 1 if params.ndim == 4 else 0
+            params = params.reshape((self.B, -1, P.nb, 10) if per_instance else (-1, P.nb, 10))
+            n_scen, pp = (params.shape[1] if per_instance else params.shape[0]), ptr(params)
+        rho = np.zeros((self.B, self.N + 1, n_scen))
+        iters = np.zeros((self.B, self.N + 1, n_scen), dtype=np.int32) if want_iters else None
+        check(self._lib.upr_batch_balance_plan(self._h, n_scen, pp, per_instance, ptr(rho), iptr(iters)))
+        return (rho, iters) if want_iters else rho
+
+    def balance_ms(self):
+        """Device time (ms) of the kernel launches of the last balance check (HIP events around them)."""
+        return float(self._lib.upr_batch_balance_ms(self._h))
+
+    def balance_forces(self, z):
+        """Contact forces f (..., nf nc), in the layout of the force block of u, from generator multipliers z (..., ncol): f = S z."""
+        return balance_forces(self.problem, z)
+
     def device_ptrs(self):
         xs, us = C.c_void_p(), C.c_void_p()
         check(self._lib.upr_batch_device_ptrs(self._h, C.byref(xs), C.byref(us)))
@@ -346,3 +413,16 @@ def core_friction_rows(problem, forces):
     out = np.zeros((n, 5 * problem.nc))
     check(_capi.lib().upr_core_friction_rows(C.byref(c), n, ptr(forces), ptr(out)))
     return out
+
+
+def balance_forces(problem, z):
+    """f = S z: the contact forces (..., nf nc) the multipliers z (..., ncol) of the balance check stand for.  With friction the
+    generators of contact i are n_i + mu_i s_i0, n_i + mu_i s_i1, n_i - mu_i s_i0, n_i - mu_i s_i1 (upright_robust/modelling.py:39-43);
+    without, z is the normal force itself."""
+    z = np.asarray(z, dtype=np.float64)
+    if problem.nf == 1:
+        return z.copy()
+    n, s, mu = np.asarray(problem.contact_normal), np.asarray(problem.contact_span).reshape(-1, 2, 3), np.asarray(problem.contact_mu)[:, None]
+    S = np.stack([n + mu * s[:, 0], n + mu * s[:, 1], n - mu * s[:, 0], n - mu * s[:, 1]], axis=2)     # (nc, 3, 4)
+    f = np.einsum("cdg,...cg->...cd", S, z.reshape(z.shape[:-1] + (problem.nc, 4)))
+    return f.reshape(z.shape[:-1] + (3 * problem.nc,))
