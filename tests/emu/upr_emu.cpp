@@ -155,14 +155,12 @@ void emu_qp(const upr_problem* P, int B, const double* xs, const double* us, con
 // ws == NULL: returns the per-instance workspace (doubles) the instantiation needs (P may be NULL then); -1: cfg is not an entry;
 // -2: P does not have cfg's shape.
 #define EMU_QP3_RUN_TIME(X) X(9, 1, 4, 3, 12, false, false, false)
-long emu_qp3_cfg(const int* cfg, const upr_problem* P, int B, const double* xs, const double* us, const double* x0, const double* lin,
-                 const double* Df, double* ws, long ws_stride, double* stats) {
-    upr_qp_args A;
-    A.P = P; A.xs = xs; A.us = us; A.x0 = x0; A.lin = lin; A.Df = Df; A.ws = ws; A.stats = stats; A.prof = nullptr;
+static long qp3_cfg_run(const int* cfg, upr_qp_args& A, int B, long ws_stride) {
+    const upr_problem* P = A.P;
 #define EMU_X(a, b, c, e, n, rows, sf, dense) \
     if (cfg[0] == a && cfg[1] == b && cfg[2] == c && cfg[3] == e && cfg[4] == n && cfg[5] == (int)rows && cfg[6] == (int)sf && cfg[7] == (int)dense) { \
         typedef upr_qp3_cfg<a, b, c, e, n, 1, rows, sf, dense> C; \
-        if (!ws) return (long)upr_qp3_ws<C>::total; \
+        if (!A.ws) return (long)upr_qp3_ws<C>::total; \
         if (!P || P->nq != a || P->nb != b || P->nc != c || P->nf != e || P->N != n) return -2; \
         A.d = upr_make_dims(P); \
         if (A.d.no > 0 && !rows) return -2; \
@@ -177,6 +175,31 @@ long emu_qp3_cfg(const int* cfg, const upr_problem* P, int B, const double* xs, 
     EMU_QP3_RUN_TIME(EMU_X)
 #undef EMU_X
     return -1;
+}
+long emu_qp3_cfg(const int* cfg, const upr_problem* P, int B, const double* xs, const double* us, const double* x0, const double* lin,
+                 const double* Df, double* ws, long ws_stride, double* stats) {
+    upr_qp_args A;
+    A.P = P; A.xs = xs; A.us = us; A.x0 = x0; A.lin = lin; A.Df = Df; A.ws = ws; A.stats = stats; A.prof = nullptr;
+    return qp3_cfg_run(cfg, A, B, ws_stride);
+}
+// The same entries with the exits the engine asks of the last QP of an advance: the feedback gains fb[B][N][nu][nx]
+// (upr_qp_args::fb, write_feedback) and the primal-dual point kkt[B][kkt_stride] (upr_qp_args::kkt) in the layout emu_qp3_export_layout
+// reports.  Same return values as emu_qp3_cfg.
+long emu_qp3_cfg_fb(const int* cfg, const upr_problem* P, int B, const double* xs, const double* us, const double* x0, const double* lin,
+                    const double* Df, double* ws, long ws_stride, double* stats, double* fb, double* kkt, long kkt_stride) {
+    upr_qp_args A;
+    A.P = P; A.xs = xs; A.us = us; A.x0 = x0; A.lin = lin; A.Df = Df; A.ws = ws; A.stats = stats; A.prof = nullptr;
+    A.fb = fb; A.kkt = kkt; A.kkt_stride = (int)kkt_stride;
+    return qp3_cfg_run(cfg, A, B, ws_stride);
+}
+// where the production kernel's export keeps the point: out[0..9] = doubles per instance, o_pi, o_nu, o_yN, o_lam, o_t, o_sig, o_tau,
+// o_gam (-1: no slack pairs for this problem), ni_stage
+void emu_qp3_export_layout(const upr_problem* P, int* out) {
+    const upr_dims d = upr_make_dims(P);
+    upr_qp_choice s;
+    upr_qp_point_exported(s, *P, d);
+    const int v[10] = {s.stride, s.o_pi, s.o_nu, s.o_yN, s.o_lam, s.o_t, s.o_sig, s.o_tau, s.o_gam, d.ni_stage};
+    std::copy(v, v + 10, out);
 }
 // the per-instance workspace of the same entries at the 256 lanes the library launches them with (emu_qp3_cfg's own figure is the
 // one-lane emulation's: the parking space of the lane-owned rows is rounded up to the workgroup); -1: cfg is not an entry

@@ -632,8 +632,8 @@ def _listed_qp3_instantiations():
 
 def test_every_qp_instantiation_has_a_screen_case():
     """Coverage guard of tests/test_gpu_qp_screen.py: every instantiation of upr_qp3_list.h has a case in its table, and the
-    emulation's exact-instantiation entry (emu_qp3_cfg) has every one of them and every run-time shape the table uses -- an
-    instantiation added to the list without a screen fails here, before any GPU time."""
+    emulation's exact-instantiation entries (emu_qp3_cfg, and emu_qp3_cfg_fb of the feedback-gain screens) have every one of them and
+    every run-time shape the table uses -- an instantiation added to the list without a screen fails here, before any GPU time."""
     import sys
     sys.path.insert(0, str(Path(__file__).resolve().parent))
     from test_gpu_qp_screen import CASES, RUN_TIME_HEADLINE
@@ -650,6 +650,15 @@ def test_every_qp_instantiation_has_a_screen_case():
         need = E.emu_qp3_cfg((C.c_int * 8)(*[int(v) for v in t]), None, 1, None, None, None, None, None, None, C.c_long(0), None)
         assert need > 0, (t, need)
     assert E.emu_qp3_cfg((C.c_int * 8)(9, 1, 4, 3, 21, 0, 0, 0), None, 1, None, None, None, None, None, None, C.c_long(0), None) == -1
+    # ... and the feedback-gain screens (tests/test_fb_reference.py, tests/test_gpu_fb_screen.py) run the same table: a threshold for
+    # every key, none above the cap, and the emulation's gain-writing entry (emu_qp3_cfg_fb) knows every one of them
+    from test_fb_reference import CAP, CASES as FB_CASES, FB_TOL
+    assert FB_CASES is CASES and set(FB_TOL) == set(CASES) and all(0.0 < v[0] <= CAP for v in FB_TOL.values())
+    E.emu_qp3_cfg_fb.restype = C.c_long
+    for t in list(CASES):
+        need = E.emu_qp3_cfg_fb((C.c_int * 8)(*[int(v) for v in t]), None, 1, None, None, None, None, None, None, C.c_long(0), None, None, None, C.c_long(0))
+        assert need > 0, (t, need)
+    assert E.emu_qp3_cfg_fb((C.c_int * 8)(9, 1, 4, 3, 21, 0, 0, 0), None, 1, None, None, None, None, None, None, C.c_long(0), None, None, None, C.c_long(0)) == -1
     # ... and the line-search table of tests/test_gpu_linesearch.py reaches all four forms of launch_linesearch
     from test_gpu_linesearch import DEVICE_CASES, GOLDEN_LS
     from test_ls_reference import EXACT, EXACT_ROWS, LARGE, SMALL, ls_case
