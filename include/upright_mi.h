@@ -366,7 +366,43 @@ double upr_batch_value_function_ms(upr_batch* h);
 int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point,
                              double* rho, double* z, int* iters);
 int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double* rho, int* iters);
-/* device time (ms) of the two kernel launches of the last balance check on the handle, HIP events around them (copies excluded) */
+/* The same two calls with friction as a scenario axis (the --mu of process_sim_runs.py): mu_scale[n_scen], finite and >= 0, scales
+ * every contact's friction coefficient in the generators of scenario s (mu_i -> mu_scale[s] mu_i; nf = 1 generators carry no mu);
+ * NULL means ones, and a scale of exactly 1 gives the answer of the call without it bit for bit.  The two calls above are these
+ * with NULL. */
+int upr_batch_balance_points_mu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point,
+                                const double* mu_scale, double* rho, double* z, int* iters);
+int upr_batch_balance_plan_mu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho,
+                              int* iters);
+
+/* ------------------------------------------------------------------------------------------------
+ * Friction margin (upright_amd/csrc/upr_margin.h): the smallest common scale kappa* on the arrangement's friction coefficients at
+ * which balancing forces exist -- one launch instead of a --mu sweep, and the signed quantity rho is not.  With rho(x; theta, kappa)
+ * the distance above on the generators of kappa mu_i,
+ *       kappa*(x; theta) = inf { kappa in [0, kappa_max] : rho(x; theta, kappa) <= 1e-8 max(|b|, 1) },   +inf if kappa_max fails
+ *   (1e-8, UPR_BAL_FEAS: the tolerance the controller's QP enforces the equality to).  kappa* < 1: balanced, 1 - kappa* of the
+ *   friction could be lost; > 1: this much more friction would have been needed; 0: normal forces alone balance the state; +inf: no
+ *   friction helps (tipping, lift-off).  The smallest friction coefficient of contact i is kappa* mu_i.  The force bounds are NOT
+ *   part of it, and kappa* carries the 1e-8 rule: it lies below the exact boundary by what that ball allows.
+ *   rho at 0, then at kappa_max, then 32 halvings (UPR_BAL_BISECT), every one a cold projection of the rho calls:
+ *       kappa_hi  the answer: the last feasible point (0: the first evaluation passed; +inf: kappa_max failed);
+ *       kappa_lo  the last infeasible point (0 with kappa_hi = 0; kappa_max with kappa_hi = +inf); kappa_hi - kappa_lo <= kappa_max 2^-32;
+ *       z         multipliers at kappa_hi: z >= 0 and |b + A(kappa_hi) z| <= 1e-8 max(|b|, 1) (zeros with kappa_hi = +inf);
+ *       y         b + A(kappa_lo) z of the projection at kappa_lo: y' a_j(kappa_lo) >= 0 for every generator and y' b > 0, so no
+ *                 forces balance the state at kappa_lo (zeros with kappa_hi = 0);
+ *       iters     least-squares solves over all evaluations, at most 34 * 3 ncol.
+ *   upr_batch_friction_margin_points  layouts of upr_batch_balance_points: kappa_hi[n][n_scen], kappa_lo likewise or NULL,
+ *       z[n][n_scen][ncol] or NULL, y[n][n_scen][6 nb] or NULL, iters[n][n_scen] or NULL.  Host pointers.
+ *   upr_batch_friction_margin_plan  the knots of the current plan on the device, as upr_batch_balance_plan (params == NULL: n_scen
+ *       == 1, every instance's own body_params): kappa_hi[B][N+1][n_scen], kappa_lo and iters likewise or NULL.
+ *   kappa_max must be finite and > 0.  Both share the scratch of the balance check, report their device time through
+ *   upr_batch_balance_ms and leave the handle as the balance check does. */
+int upr_batch_friction_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point,
+                                     double kappa_max, double* kappa_hi, double* kappa_lo, double* z, double* y, int* iters);
+int upr_batch_friction_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double kappa_max,
+                                   double* kappa_hi, double* kappa_lo, int* iters);
+/* device time (ms) of the two kernel launches of the last balance check or friction margin on the handle, HIP events around them
+ * (copies excluded) */
 double upr_batch_balance_ms(upr_batch* h);
 
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):

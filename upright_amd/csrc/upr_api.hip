@@ -33,6 +33,7 @@
 #include "upr_qp_select.h"
 #include "upr_value.h"
 #include "upr_balance.h"
+#include "upr_margin.h"
 
 namespace {
 
@@ -871,8 +872,12 @@ int balance_check_params(const upr_batch* h, const double* params, size_t count)
         if (!(params[10 * i] > 0) || !std::isfinite(params[10 * i])) return fail("balance check: every body of every scenario needs a positive finite mass");
     return 0;
 }
+// mu_scale_host: the friction scale of every scenario ([n_scen]) or NULL: ones.  mar: NULL for the rho calls; else the friction-margin
+// call (upr_margin.h) on the same jobs -- rho is not written, z is the one at kappa_hi, iters the solves over all evaluations.
+struct bal_margin_out { double kappa_max; double* hi; double* lo; double* y; };
 int balance_run(upr_batch* h, long long n, const double* x_host, const double* dx, int n_scen, const double* params_host, size_t params_count,
-                const double* dparams, int pdiv, double* rho, double* z, int* iters) {
+                const double* dparams, int pdiv, double* rho, double* z, int* iters, const double* mu_scale_host = nullptr,
+                const bal_margin_out* mar = nullptr) {
     const upr_dims& d = h->d;
     const upr_bal_dims L = upr_bal_layout(d.nb, d.nc, d.nf);
     const long long njobs = n * n_scen;
@@ -880,10 +885,14 @@ int balance_run(upr_batch* h, long long n, const double* x_host, const double* d
     const size_t o_st = 0, o_rho = o_st + bal_up(sizeof(double) * n * UPR_BAL_ST), o_z = o_rho + bal_up(sizeof(double) * njobs),
                  o_it = o_z + (z ? bal_up(sizeof(double) * njobs * L.ncol) : 0), o_par = o_it + (iters ? bal_up(sizeof(int) * njobs) : 0),
                  o_x = o_par + (params_host ? bal_up(sizeof(double) * params_count * d.nb * 10) : 0),
-                 total = o_x + (x_host ? bal_up(sizeof(double) * n * d.nx) : 0);
+                 o_mu = o_x + (x_host ? bal_up(sizeof(double) * n * d.nx) : 0),
+                 o_lo = o_mu + (mu_scale_host ? bal_up(sizeof(double) * n_scen) : 0),
+                 o_y = o_lo + ((mar && mar->lo) ? bal_up(sizeof(double) * njobs) : 0),
+                 total = o_y + ((mar && mar->y) ? bal_up(sizeof(double) * njobs * L.m) : 0);
     if (balance_scratch(h, total)) return 1;
     char* base = (char*)h->bal_buf;
     double* dst = (double*)(base + o_st); double* drho = (double*)(base + o_rho); double* dz = (double*)(base + o_z); int* dit = (int*)(base + o_it);
+    double* dlo = (double*)(base + o_lo); double* dy = (double*)(base + o_y);
     if (params_host) {
         UPR_HIP(hipMemcpyAsync(base + o_par, params_host, sizeof(double) * params_count * d.nb * 10, hipMemcpyHostToDevice, h->stream));
         dparams = (const double*)(base + o_par);
@@ -892,6 +901,7 @@ int balance_run(upr_batch* h, long long n, const double* x_host, const double* d
         UPR_HIP(hipMemcpyAsync(base + o_x, x_host, sizeof(double) * n * d.nx, hipMemcpyHostToDevice, h->stream));
         dx = (const double*)(base + o_x);
     }
+    if (mu_scale_host) UPR_HIP(hipMemcpyAsync(base + o_mu, mu_scale_host, sizeof(double) * n_scen, hipMemcpyHostToDevice, h->stream));
     if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
     UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
     const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
@@ -901,23 +911,42 @@ int balance_run(upr_batch* h, long long n, const double* x_host, const double* d
     upr_bal_args A;
     A.P = h->dP; A.n = (int)n; A.n_scen = n_scen; A.st = dst; A.params = dparams; A.pdiv = pdiv; A.eq_scale = d.eq_scale;
     A.rho = drho; A.z = z ? dz : nullptr; A.iters = iters ? dit : nullptr;
+    A.mu_scale = mu_scale_host ? (const double*)(base + o_mu) : nullptr;
+    upr_mar_args M;
+    if (mar) { M.J = A; M.J.rho = nullptr; M.kappa_max = mar->kappa_max; M.kappa_hi = drho; M.kappa_lo = mar->lo ? dlo : nullptr; M.y = mar->y ? dy : nullptr; }
+    // the wave-per-job kernels: jobs are dealt round robin to a grid that fills the device a few times over (a workgroup is one
+    // wave; its LDS, at most 26.4 KB, lets six of the largest shape share a CU inside the 160 KiB)
+    const dim3 lane_grid((unsigned)((njobs + 63) / 64)), wave_grid((unsigned)(njobs < 16384 ? njobs : 16384));
+    const size_t lds = (size_t)L.total * sizeof(double);
     if (upr_bal_lane_form(d.nb) && h->bal_lane) {
-        hipLaunchKernelGGL(upr_bal_project1_kernel, dim3((unsigned)((njobs + 63) / 64)), dim3(64), 0, h->stream, A, L, njobs);
+        if (mar) hipLaunchKernelGGL(upr_bal_margin1_kernel, lane_grid, dim3(64), 0, h->stream, M, L, njobs);
+        else if (A.mu_scale) hipLaunchKernelGGL(upr_bal_project1_mu_kernel, lane_grid, dim3(64), 0, h->stream, A, L, njobs);
+        else hipLaunchKernelGGL(upr_bal_project1_kernel, lane_grid, dim3(64), 0, h->stream, A, L, njobs);
     } else {
-        // jobs are dealt round robin to a grid that fills the device a few times over (a workgroup is one wave; its LDS, at most
-        // 26.4 KB, lets six of the largest shape share a CU inside the 160 KiB)
-        const long long grid = njobs < 16384 ? njobs : 16384;
-        hipLaunchKernelGGL(upr_bal_project_kernel, dim3((unsigned)grid), dim3(64), (size_t)L.total * sizeof(double), h->stream, A, L, njobs);
+        if (mar) hipLaunchKernelGGL(upr_bal_margin_kernel, wave_grid, dim3(64), lds, h->stream, M, L, njobs);
+        else if (A.mu_scale) hipLaunchKernelGGL(upr_bal_project_mu_kernel, wave_grid, dim3(64), lds, h->stream, A, L, njobs);
+        else hipLaunchKernelGGL(upr_bal_project_kernel, wave_grid, dim3(64), lds, h->stream, A, L, njobs);
     }
     UPR_HIP(hipGetLastError());
     UPR_HIP(hipEventRecord(h->bal_ev[1], h->stream));
-    UPR_HIP(hipMemcpyAsync(rho, drho, sizeof(double) * njobs, hipMemcpyDeviceToHost, h->stream));
+    UPR_HIP(hipMemcpyAsync(mar ? mar->hi : rho, drho, sizeof(double) * njobs, hipMemcpyDeviceToHost, h->stream));
     if (z) UPR_HIP(hipMemcpyAsync(z, dz, sizeof(double) * njobs * L.ncol, hipMemcpyDeviceToHost, h->stream));
     if (iters) UPR_HIP(hipMemcpyAsync(iters, dit, sizeof(int) * njobs, hipMemcpyDeviceToHost, h->stream));
+    if (mar && mar->lo) UPR_HIP(hipMemcpyAsync(mar->lo, dlo, sizeof(double) * njobs, hipMemcpyDeviceToHost, h->stream));
+    if (mar && mar->y) UPR_HIP(hipMemcpyAsync(mar->y, dy, sizeof(double) * njobs * L.m, hipMemcpyDeviceToHost, h->stream));
     UPR_HIP(hipStreamSynchronize(h->stream));
     float ms = 0.0f;
     UPR_HIP(hipEventElapsedTime(&ms, h->bal_ev[0], h->bal_ev[1]));
     h->bal_ms = ms;
+    return 0;
+}
+int balance_check_mu(const double* mu_scale, int n_scen) {
+    if (mu_scale) for (int s = 0; s < n_scen; ++s)
+        if (!(mu_scale[s] >= 0) || !std::isfinite(mu_scale[s])) return fail("balance check: every mu_scale must be finite and >= 0");
+    return 0;
+}
+int balance_check_kappa(double kappa_max) {
+    if (!(kappa_max > 0) || !std::isfinite(kappa_max)) return fail("friction margin: kappa_max must be finite and > 0");
     return 0;
 }
 
@@ -1599,28 +1628,64 @@ double upr_batch_value_function_ms(upr_batch* h) {
     return h->vf_ms;
 }
 
-int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double* rho, double* z, int* iters) {
+int upr_batch_balance_points_mu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, const double* mu_scale,
+                                double* rho, double* z, int* iters) {
     UPR_ENTER(h);
     if (n <= 0) return 0;
     if (!x || !params || !rho) return fail("upr_batch_balance_points: x, params and rho must not be NULL");
     if (n_scen < 1) return fail("upr_batch_balance_points: n_scen must be >= 1");
     const size_t count = (size_t)(per_point ? n : 1) * n_scen;
-    if (balance_check_params(h, params, count)) return 1;
-    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, rho, z, iters);
+    if (balance_check_params(h, params, count) || balance_check_mu(mu_scale, n_scen)) return 1;
+    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, rho, z, iters, mu_scale);
+}
+int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double* rho, double* z, int* iters) {
+    return upr_batch_balance_points_mu(h, n, x, n_scen, params, per_point, nullptr, rho, z, iters);
 }
 
-int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double* rho, int* iters) {
-    UPR_ENTER(h);
-    if (!rho) return fail("upr_batch_balance_plan: rho must not be NULL");
+// the plan's knots: the jobs of both plan calls (rho, or with mar the friction margin)
+static int balance_plan_run(upr_batch* h, const char* who, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho,
+                            double* z, int* iters, const bal_margin_out* mar) {
     const long long n = (long long)h->B * (h->d.N + 1);
     if (!params) {   // the nominal check: every instance against its own body parameters
-        if (n_scen != 1) return fail("upr_batch_balance_plan: params == NULL needs n_scen == 1 (every instance's own body parameters)");
-        return balance_run(h, n, nullptr, h->xs, 1, nullptr, 0, h->body_params, h->d.N + 1, rho, nullptr, iters);
+        if (n_scen != 1) return fail(std::string(who) + ": params == NULL needs n_scen == 1 (every instance's own body parameters)");
+        if (balance_check_mu(mu_scale, 1)) return 1;
+        return balance_run(h, n, nullptr, h->xs, 1, nullptr, 0, h->body_params, h->d.N + 1, rho, z, iters, mu_scale, mar);
     }
-    if (n_scen < 1) return fail("upr_batch_balance_plan: n_scen must be >= 1");
+    if (n_scen < 1) return fail(std::string(who) + ": n_scen must be >= 1");
     const size_t count = (size_t)(per_instance ? h->B : 1) * n_scen;
+    if (balance_check_params(h, params, count) || balance_check_mu(mu_scale, n_scen)) return 1;
+    return balance_run(h, n, nullptr, h->xs, n_scen, params, count, nullptr, per_instance ? h->d.N + 1 : 0, rho, z, iters, mu_scale, mar);
+}
+
+int upr_batch_balance_plan_mu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho, int* iters) {
+    UPR_ENTER(h);
+    if (!rho) return fail("upr_batch_balance_plan: rho must not be NULL");
+    return balance_plan_run(h, "upr_batch_balance_plan", n_scen, params, per_instance, mu_scale, rho, nullptr, iters, nullptr);
+}
+int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double* rho, int* iters) {
+    return upr_batch_balance_plan_mu(h, n_scen, params, per_instance, nullptr, rho, iters);
+}
+
+int upr_batch_friction_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double kappa_max,
+                                     double* kappa_hi, double* kappa_lo, double* z, double* y, int* iters) {
+    UPR_ENTER(h);
+    if (balance_check_kappa(kappa_max)) return 1;
+    if (n <= 0) return 0;
+    if (!x || !params || !kappa_hi) return fail("upr_batch_friction_margin_points: x, params and kappa_hi must not be NULL");
+    if (n_scen < 1) return fail("upr_batch_friction_margin_points: n_scen must be >= 1");
+    const size_t count = (size_t)(per_point ? n : 1) * n_scen;
     if (balance_check_params(h, params, count)) return 1;
-    return balance_run(h, n, nullptr, h->xs, n_scen, params, count, nullptr, per_instance ? h->d.N + 1 : 0, rho, nullptr, iters);
+    const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, y};
+    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, nullptr, z, iters, nullptr, &mar);
+}
+
+int upr_batch_friction_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double kappa_max, double* kappa_hi,
+                                   double* kappa_lo, int* iters) {
+    UPR_ENTER(h);
+    if (balance_check_kappa(kappa_max)) return 1;
+    if (!kappa_hi) return fail("upr_batch_friction_margin_plan: kappa_hi must not be NULL");
+    const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, nullptr};
+    return balance_plan_run(h, "upr_batch_friction_margin_plan", n_scen, params, per_instance, nullptr, nullptr, nullptr, iters, &mar);
 }
 
 double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }

@@ -87,6 +87,9 @@ struct upr_bal_args {
     double* rho;             // [n][n_scen]
     double* z;               // [n][n_scen][ncol] or NULL
     int* iters;              // [n][n_scen] or NULL
+    // friction scale of every scenario, [n_scen] -- the generators of contact i are formed with mu_scale[sc] mu_i (the --mu of
+    // process_sim_runs.py as a scenario axis); read by the _mu kernels only
+    const double* mu_scale = nullptr;
 };
 
 // ---- state kernel body: one point ---------------------------------------------------------------------------------------------
@@ -99,12 +102,15 @@ static UPR_HDI void upr_bal_state_point(const upr_problem* P, const double* x, d
 }
 
 // ---- column j of A: the blocks on contact_body1 (ba = -1: the end effector, no block) and contact_body2 ----------------------------
-static UPR_HDI void upr_bal_column(const upr_problem* P, const double* bp, double scale, int gpc, int j, int* ba, double* va, int* bb, double* vb) {
+// kap: the friction scale, the pyramid of contact i is built on kap mu_i (kap = 1: mu_i * 1.0 is exact, the column is bit for bit
+// the one without a scale; nf = 1 generators carry no mu)
+static UPR_HDI void upr_bal_column(const upr_problem* P, const double* bp, double scale, int gpc, int j, int* ba, double* va, int* bb, double* vb,
+                                   double kap = 1.0) {
     const int i = j / gpc, g = j - i * gpc;
     double d[3];
     for (int a = 0; a < 3; ++a) d[a] = P->contact_normal[i][a];
     if (gpc == 4) {
-        const double sm = ((g < 2) ? 1.0 : -1.0) * P->contact_mu[i];
+        const double sm = ((g < 2) ? 1.0 : -1.0) * (P->contact_mu[i] * kap);
         const double* s = P->contact_span[i] + 3 * (g & 1);
         for (int a = 0; a < 3; ++a) d[a] += sm * s[a];
     }
@@ -223,28 +229,16 @@ static UPR_HDI void upr_bal_solve(const upr_ctx& ctx, int mp, int np, const doub
     }
 }
 
-// ---- one (point, scenario) job: the lanes of ctx work on it together, W: L.total doubles of workspace (LDS) -------------------------
-static UPR_HDI void upr_bal_job(const upr_ctx& ctx, const upr_bal_args& A, const upr_bal_dims& L, long long job, double* W) {
-    const upr_problem* P = A.P;
-    const int nb = P->nb, m = L.m, ncol = L.ncol, mp = L.mp;
-    const long long pt = job / A.n_scen;
-    const int sc = (int)(job - pt * A.n_scen);
-    const double* bp = A.params + (size_t)10 * nb * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
-    const double* st = A.st + (size_t)pt * UPR_BAL_ST;
+// ---- the projection of one job: the lanes of ctx work on it together, W: L.total doubles of workspace (LDS) -------------------------
+// b (W + L.o_b) is written by the caller, not yet synchronised; kap: the friction scale of the generators.  A cold start: nothing of
+// an earlier projection in W is read.  Leaves r = b + A z (W + L.o_r), the passive slots (zp, pidx, their columns; *np_out of them),
+// the column states and in G the Cholesky factor of the last passive system (its leading block is the factor of the slots that
+// are left unless the cap was reached); returns rho on every lane, *bnorm_out = |b|, *iters_out the least-squares solves (the cap if it was reached).
+static UPR_HDI double upr_bal_project(const upr_ctx& ctx, const upr_problem* P, const upr_bal_dims& L, const double* bp, double eq_scale,
+                                      double kap, double* W, int* np_out, int* iters_out, double* bnorm_out) {
+    const int m = L.m, ncol = L.ncol, mp = L.mp;
     double *b = W + L.o_b, *r = W + L.o_r, *zp = W + L.o_zp, *s = W + L.o_s, *y = W + L.o_y, *dg = W + L.o_dg, *pc = W + L.o_pcol, *G = W + L.o_G;
     int* pidx = (int*)(W + L.o_int); int* pb = pidx + mp; int* flag = pb + 2 * mp;
-
-    UPR_WSYNC();   // (the previous job of this wave is done with the workspace)
-    // b = g(x, 0; theta): the residual of every body without contact wrench, scaled as the linearisation scales it
-    UPR_FOR(k, nb) {
-        upr_ee<double> E;
-        for (int i = 0; i < 9; ++i) E.C[i] = st[i];
-        for (int i = 0; i < 3; ++i) { E.w[i] = st[9 + i]; E.al[i] = st[12 + i]; E.a[i] = st[15 + i]; E.p[i] = 0.0; E.v[i] = 0.0; }
-        const double zero3[3] = {0.0, 0.0, 0.0};
-        double gb[6];
-        upr_body_residual<double>(E, bp + 10 * k, P->gravity, zero3, zero3, gb);
-        for (int c = 0; c < 6; ++c) b[6 * k + c] = A.eq_scale * gb[c];
-    }
     UPR_FOR(j, ncol) flag[j] = 0;
     UPR_WSYNC();
     double bb2 = 0.0;
@@ -265,7 +259,7 @@ static UPR_HDI void upr_bal_job(const upr_ctx& ctx, const upr_bal_args& A, const
             UPR_FOR(j, ncol) {
                 if (flag[j] != 0) continue;
                 int ba, bq; double va[6], vb[6];
-                upr_bal_column(P, bp, A.eq_scale, L.gpc, j, &ba, va, &bq, vb);
+                upr_bal_column(P, bp, eq_scale, L.gpc, j, &ba, va, &bq, vb, kap);
                 double w = 0.0, n2 = 0.0;
                 for (int c = 0; c < 6; ++c) { w -= vb[c] * r[6 * bq + c]; n2 += vb[c] * vb[c]; }
                 if (ba >= 0) for (int c = 0; c < 6; ++c) { w -= va[c] * r[6 * ba + c]; n2 += va[c] * va[c]; if (ba == bq) n2 += 2.0 * va[c] * vb[c]; }
@@ -283,7 +277,7 @@ static UPR_HDI void upr_bal_job(const upr_ctx& ctx, const upr_bal_args& A, const
         UPR_WSYNC();
         if (ctx.tid == 0) {
             int ba, bq; double va[6], vb[6];
-            upr_bal_column(P, bp, A.eq_scale, L.gpc, bj, &ba, va, &bq, vb);
+            upr_bal_column(P, bp, eq_scale, L.gpc, bj, &ba, va, &bq, vb, kap);
             for (int c = 0; c < 6; ++c) { pc[12 * np + c] = va[c]; pc[12 * np + 6 + c] = vb[c]; }
             pb[2 * np] = ba; pb[2 * np + 1] = bq; pidx[np] = bj; zp[np] = 0.0; flag[bj] = 1;
         }
@@ -369,18 +363,53 @@ static UPR_HDI void upr_bal_job(const upr_ctx& ctx, const upr_bal_args& A, const
     if (capped) { upr_bal_residual(ctx, L, np, b, pc, pb, zp, r); iters = cap; }
     double rr = 0.0;
     for (int e = 0; e < m; ++e) rr += r[e] * r[e];
+    *np_out = np; *iters_out = iters; *bnorm_out = bnorm;
+    return sqrt(rr);
+}
+
+// b = g(x, 0; theta) of a job into W + L.o_b: the residual of every body without contact wrench, scaled as the linearisation scales
+// it (bodies over the lanes; the caller synchronises -- upr_bal_project does)
+static UPR_HDI void upr_bal_rhs(const upr_ctx& ctx, const upr_problem* P, const double* st, const double* bp, double eq_scale, double* b) {
+    UPR_FOR(k, P->nb) {
+        upr_ee<double> E;
+        for (int i = 0; i < 9; ++i) E.C[i] = st[i];
+        for (int i = 0; i < 3; ++i) { E.w[i] = st[9 + i]; E.al[i] = st[12 + i]; E.a[i] = st[15 + i]; E.p[i] = 0.0; E.v[i] = 0.0; }
+        const double zero3[3] = {0.0, 0.0, 0.0};
+        double gb[6];
+        upr_body_residual<double>(E, bp + 10 * k, P->gravity, zero3, zero3, gb);
+        for (int c = 0; c < 6; ++c) b[6 * k + c] = eq_scale * gb[c];
+    }
+}
+// the multipliers of the passive slots, scattered to the ncol entries of zo (columns over the lanes)
+static UPR_HDI void upr_bal_put_z(const upr_ctx& ctx, const upr_bal_dims& L, const double* W, int np, double* zo) {
+    const double* zp = W + L.o_zp;
+    const int* pidx = (const int*)(W + L.o_int); const int* flag = pidx + 3 * L.mp;
+    UPR_FOR(j, L.ncol) {
+        double v = 0.0;
+        if (flag[j] == 1) for (int t = 0; t < np; ++t) if (pidx[t] == j) v = zp[t];
+        zo[j] = v;
+    }
+}
+
+// ---- one (point, scenario) job ------------------------------------------------------------------------------------------------------
+// MU: the friction scale of the job's scenario is read from A.mu_scale; without it the scale is the constant 1 and folds away (the
+// kernels of the calls without a friction scale keep the code they had before there was one)
+template <bool MU = false>
+static UPR_HDI void upr_bal_job(const upr_ctx& ctx, const upr_bal_args& A, const upr_bal_dims& L, long long job, double* W) {
+    const upr_problem* P = A.P;
+    const long long pt = job / A.n_scen;
+    const int sc = (int)(job - pt * A.n_scen);
+    const double* bp = A.params + (size_t)10 * P->nb * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
+    const double kap = MU ? A.mu_scale[sc] : 1.0;
+    UPR_WSYNC();   // (the previous job of this wave is done with the workspace)
+    upr_bal_rhs(ctx, P, A.st + (size_t)pt * UPR_BAL_ST, bp, A.eq_scale, W + L.o_b);
+    int np, iters; double bnorm;
+    const double rho = upr_bal_project(ctx, P, L, bp, A.eq_scale, kap, W, &np, &iters, &bnorm);
     if (ctx.tid == 0) {
-        A.rho[job] = sqrt(rr);
+        A.rho[job] = rho;
         if (A.iters) A.iters[job] = iters;
     }
-    if (A.z) {
-        double* zo = A.z + (size_t)job * ncol;
-        UPR_FOR(j, ncol) {
-            double v = 0.0;
-            if (flag[j] == 1) for (int t = 0; t < np; ++t) if (pidx[t] == j) v = zp[t];
-            zo[j] = v;
-        }
-    }
+    if (A.z) upr_bal_put_z(ctx, L, W, np, A.z + (size_t)job * L.ncol);
 }
 
 // ---- one-body arrangements: a lane per job ------------------------------------------------------------------------------------------
@@ -390,39 +419,28 @@ static UPR_HDI void upr_bal_job(const upr_ctx& ctx, const upr_bal_args& A, const
 // in scratch; the sets of passive and barred columns are bit masks (up to 128 columns: 32 contacts).
 #define UPR_BAL1_MP 6
 static UPR_HDI bool upr_bal_bit(unsigned long long lo, unsigned long long hi, int j) { return (((j < 64) ? lo : hi) >> (j & 63)) & 1ull; }
-static UPR_HDI void upr_bal_column1(const upr_problem* P, const double* bp, double scale, int gpc, int j, double* v) {
+static UPR_HDI void upr_bal_column1(const upr_problem* P, const double* bp, double scale, int gpc, int j, double* v, double kap = 1.0) {
     int ba, bb; double va[6], vb[6];
-    upr_bal_column(P, bp, scale, gpc, j, &ba, va, &bb, vb);
+    upr_bal_column(P, bp, scale, gpc, j, &ba, va, &bb, vb, kap);
     for (int c = 0; c < 6; ++c) v[c] = (ba >= 0) ? va[c] + vb[c] : vb[c];
 }
-static UPR_HDI void upr_bal_job1(const upr_bal_args& A, const upr_bal_dims& L, long long job) {
+// The projection of one job on one lane, cold: b the right-hand side, thr = UPR_BAL_TOL max(|b|, 1), kap the friction scale of the
+// generators.  Leaves r = b + A z, the passive slots (pidx, zp, their columns pc; np of them) and in G the Cholesky factor of the
+// last passive system (its leading np x np block is the factor of the np slots unless the cap was reached); returns the
+// least-squares solves (the cap if reached).
+static UPR_HDI int upr_bal_project1(const upr_problem* P, const upr_bal_dims& L, const double* bp, double eq_scale, double kap, const double (&b)[6],
+                                    double thr, double (&r)[6], double (&zp)[UPR_BAL1_MP], int (&pidx)[UPR_BAL1_MP], int& np,
+                                    double (&pc)[UPR_BAL1_MP][6], double (&G)[UPR_BAL1_MP][UPR_BAL1_MP]) {
     constexpr int MP = UPR_BAL1_MP;
-    const upr_problem* P = A.P;
     const int ncol = L.ncol, mp = L.mp;
-    const long long pt = job / A.n_scen;
-    const int sc = (int)(job - pt * A.n_scen);
-    const double* bp = A.params + (size_t)10 * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
-    const double* st = A.st + (size_t)pt * UPR_BAL_ST;
-    double b[6], r[6], pc[MP][6], zp[MP], s[MP], y[MP], dg[MP], G[MP][MP];
-    int pidx[MP];
-    {
-        upr_ee<double> E;
-        for (int i = 0; i < 9; ++i) E.C[i] = st[i];
-        for (int i = 0; i < 3; ++i) { E.w[i] = st[9 + i]; E.al[i] = st[12 + i]; E.a[i] = st[15 + i]; E.p[i] = 0.0; E.v[i] = 0.0; }
-        const double zero3[3] = {0.0, 0.0, 0.0};
-        double gb[6];
-        upr_body_residual<double>(E, bp, P->gravity, zero3, zero3, gb);
-        for (int c = 0; c < 6; ++c) b[c] = A.eq_scale * gb[c];
-    }
+    double s[MP], y[MP], dg[MP];
 #pragma unroll
     for (int t = 0; t < MP; ++t) { zp[t] = 0.0; s[t] = 0.0; pidx[t] = 0; for (int c = 0; c < 6; ++c) pc[t][c] = 0.0; }
-    double bb2 = 0.0;
-    for (int c = 0; c < 6; ++c) bb2 += b[c] * b[c];
-    const double bnorm = sqrt(bb2), thr = UPR_BAL_TOL * (bnorm > 1.0 ? bnorm : 1.0);
     const int cap = upr_bal_iter_cap(ncol);
     unsigned long long pas0 = 0, pas1 = 0, bar0 = 0, bar1 = 0;
-    int np = 0, iters = 0;
+    int iters = 0;
     bool capped = false;
+    np = 0;
 
     while (true) {
         for (int c = 0; c < 6; ++c) r[c] = b[c];
@@ -436,7 +454,7 @@ static UPR_HDI void upr_bal_job1(const upr_bal_args& A, const upr_bal_dims& L, l
             for (int j = 0; j < ncol; ++j) {
                 if (upr_bal_bit(pas0 | bar0, pas1 | bar1, j)) continue;
                 double v[6];
-                upr_bal_column1(P, bp, A.eq_scale, L.gpc, j, v);
+                upr_bal_column1(P, bp, eq_scale, L.gpc, j, v, kap);
                 double w = 0.0, n2 = 0.0;
                 for (int c = 0; c < 6; ++c) { w -= v[c] * r[c]; n2 += v[c] * v[c]; }
                 const double nrm = sqrt(n2);
@@ -452,7 +470,7 @@ static UPR_HDI void upr_bal_job1(const upr_bal_args& A, const upr_bal_dims& L, l
         if (iters >= cap) { capped = true; break; }
         {
             double v[6];
-            upr_bal_column1(P, bp, A.eq_scale, L.gpc, bj, v);
+            upr_bal_column1(P, bp, eq_scale, L.gpc, bj, v, kap);
 #pragma unroll
             for (int t = 0; t < MP; ++t) if (t == np) { for (int c = 0; c < 6; ++c) pc[t][c] = v[c]; pidx[t] = bj; zp[t] = 0.0; }
             if (bj < 64) pas0 |= 1ull << bj; else pas1 |= 1ull << (bj - 64);
@@ -580,16 +598,42 @@ static UPR_HDI void upr_bal_job1(const upr_bal_args& A, const upr_bal_dims& L, l
         for (int t = 0; t < MP; ++t) if (t < np) for (int c = 0; c < 6; ++c) r[c] += zp[t] * pc[t][c];
         iters = cap;
     }
+    return iters;
+}
+// b = g(x, 0; theta) of a one-body job
+static UPR_HDI void upr_bal_rhs1(const upr_problem* P, const double* st, const double* bp, double eq_scale, double (&b)[6]) {
+    upr_ee<double> E;
+    for (int i = 0; i < 9; ++i) E.C[i] = st[i];
+    for (int i = 0; i < 3; ++i) { E.w[i] = st[9 + i]; E.al[i] = st[12 + i]; E.a[i] = st[15 + i]; E.p[i] = 0.0; E.v[i] = 0.0; }
+    const double zero3[3] = {0.0, 0.0, 0.0};
+    double gb[6];
+    upr_body_residual<double>(E, bp, P->gravity, zero3, zero3, gb);
+    for (int c = 0; c < 6; ++c) b[c] = eq_scale * gb[c];
+}
+static UPR_HDI void upr_bal_put_z1(int ncol, const double (&zp)[UPR_BAL1_MP], const int (&pidx)[UPR_BAL1_MP], int np, double* zo) {
+    for (int j = 0; j < ncol; ++j) zo[j] = 0.0;
+#pragma unroll
+    for (int t = 0; t < UPR_BAL1_MP; ++t) if (t < np) zo[pidx[t]] = zp[t];
+}
+template <bool MU = false>
+static UPR_HDI void upr_bal_job1(const upr_bal_args& A, const upr_bal_dims& L, long long job) {
+    const upr_problem* P = A.P;
+    const long long pt = job / A.n_scen;
+    const int sc = (int)(job - pt * A.n_scen);
+    const double* bp = A.params + (size_t)10 * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
+    const double kap = MU ? A.mu_scale[sc] : 1.0;
+    double b[6], r[6], zp[UPR_BAL1_MP], pc[UPR_BAL1_MP][6], G[UPR_BAL1_MP][UPR_BAL1_MP];
+    int pidx[UPR_BAL1_MP], np;
+    upr_bal_rhs1(P, A.st + (size_t)pt * UPR_BAL_ST, bp, A.eq_scale, b);
+    double bb2 = 0.0;
+    for (int c = 0; c < 6; ++c) bb2 += b[c] * b[c];
+    const double bnorm = sqrt(bb2), thr = UPR_BAL_TOL * (bnorm > 1.0 ? bnorm : 1.0);
+    const int iters = upr_bal_project1(P, L, bp, A.eq_scale, kap, b, thr, r, zp, pidx, np, pc, G);
     double rr = 0.0;
     for (int c = 0; c < 6; ++c) rr += r[c] * r[c];
     A.rho[job] = sqrt(rr);
     if (A.iters) A.iters[job] = iters;
-    if (A.z) {
-        double* zo = A.z + (size_t)job * ncol;
-        for (int j = 0; j < ncol; ++j) zo[j] = 0.0;
-#pragma unroll
-        for (int t = 0; t < MP; ++t) if (t < np) zo[pidx[t]] = zp[t];
-    }
+    if (A.z) upr_bal_put_z1(L.ncol, zp, pidx, np, A.z + (size_t)job * L.ncol);
 }
 
 // which of the two forms a problem runs: one body -> a lane per job (upr_bal_job1), else a wave per job (upr_bal_job)
@@ -612,5 +656,15 @@ __global__ __launch_bounds__(64) void upr_bal_project_kernel(upr_bal_args A, upr
 __global__ __launch_bounds__(64) void upr_bal_project1_kernel(upr_bal_args A, upr_bal_dims L, long long njobs) {
     const long long job = (long long)blockIdx.x * 64 + threadIdx.x;
     if (job < njobs) upr_bal_job1(A, L, job);
+}
+// the two with a friction scale per scenario (A.mu_scale)
+__global__ __launch_bounds__(64) void upr_bal_project_mu_kernel(upr_bal_args A, upr_bal_dims L, long long njobs) {
+    extern __shared__ double upr_bal_lds[];
+    upr_ctx ctx; ctx.tid = threadIdx.x; ctx.nt = 64;
+    for (long long job = blockIdx.x; job < njobs; job += gridDim.x) upr_bal_job<true>(ctx, A, L, job, upr_bal_lds);
+}
+__global__ __launch_bounds__(64) void upr_bal_project1_mu_kernel(upr_bal_args A, upr_bal_dims L, long long njobs) {
+    const long long job = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (job < njobs) upr_bal_job1<true>(A, L, job);
 }
 #endif

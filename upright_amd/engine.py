@@ -284,12 +284,14 @@ class BatchMPC:
         normal alone without."""
         return self.problem.nc * (4 if self.problem.nf == 3 else 1)
 
-    def balance_check(self, x, params, want_z=False, want_iters=False):
+    def balance_check(self, x, params, want_z=False, want_iters=False, mu_scale=None):
         """rho (n, n_scen): the distance of the wrench the bodies need at the robot states x (n, 3 nq) to the contact wrench cone of
         the arrangement, under the inertial parameters params (n_scen, nb, 10) shared by all points or (n, n_scen, nb, 10) per
         point -- 0 if and only if balancing forces exist (upr_batch_balance_points; the force bounds are not part of it).  With
         want_z / want_iters the tuple (rho, z (n, n_scen, ncol), iters (n, n_scen)) restricted to what was asked for; z are the
-        multipliers of the cone generators (balance_forces turns them into contact forces).
+        multipliers of the cone generators (balance_forces turns them into contact forces).  mu_scale (a number or one per scenario,
+        finite and >= 0): every contact's friction coefficient is scaled by it in that scenario (the --mu of process_sim_runs.py as
+        a scenario axis, upr_batch_balance_points_mu); None and 1 give the same bits.
 
         The study's sweep (upright_robust/scripts/planning_sim_loop.py:548-559,613-616: the centre of mass at the centre, the face
         centres and the vertices of its box, times three inertia scales = 45 scenarios) for a one-body arrangement:
@@ -315,29 +317,85 @@ class BatchMPC:
         rho = np.zeros((n, n_scen))
         z = np.zeros((n, n_scen, self.balance_columns)) if want_z else None
         iters = np.zeros((n, n_scen), dtype=np.int32) if want_iters else None
-        check(self._lib.upr_batch_balance_points(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, ptr(rho), ptr(z), iptr(iters)))
+        mu = self._mu_scale(mu_scale, n_scen)
+        check(self._lib.upr_batch_balance_points_mu(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, ptr(mu), ptr(rho), ptr(z), iptr(iters)))
         out = (rho,) + ((z,) if want_z else ()) + ((iters,) if want_iters else ())
         return out[0] if len(out) == 1 else out
 
-    def balance_check_plan(self, params=None, want_iters=False):
+    @staticmethod
+    def _mu_scale(mu_scale, n_scen):
+        if mu_scale is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(mu_scale, dtype=np.float64), (n_scen,)))
+
+    def balance_check_plan(self, params=None, want_iters=False, mu_scale=None):
         """rho (B, N + 1, n_scen) at the knots of the current plan, evaluated where they lie on the device (upr_batch_balance_plan).
         params None: every instance against its own body parameters (n_scen = 1, the nominal check); (n_scen, nb, 10): the same
-        scenarios for every instance; (B, n_scen, nb, 10): per instance."""
-        P = self.problem
-        if params is None:
-            n_scen, per_instance, pp = 1, 0, None
-        else:
-            params = cont(params)
-            per_instance = 1 if params.ndim == 4 else 0
-            params = params.reshape((self.B, -1, P.nb, 10) if per_instance else (-1, P.nb, 10))
-            n_scen, pp = (params.shape[1] if per_instance else params.shape[0]), ptr(params)
+        scenarios for every instance; (B, n_scen, nb, 10): per instance.  mu_scale as in balance_check."""
+        n_scen, per_instance, params = self._plan_params(params)
         rho = np.zeros((self.B, self.N + 1, n_scen))
         iters = np.zeros((self.B, self.N + 1, n_scen), dtype=np.int32) if want_iters else None
-        check(self._lib.upr_batch_balance_plan(self._h, n_scen, pp, per_instance, ptr(rho), iptr(iters)))
+        mu = self._mu_scale(mu_scale, n_scen)
+        check(self._lib.upr_batch_balance_plan_mu(self._h, n_scen, ptr(params), per_instance, ptr(mu), ptr(rho), iptr(iters)))
         return (rho, iters) if want_iters else rho
 
+    def _plan_params(self, params):
+        if params is None:
+            return 1, 0, None
+        P = self.problem
+        params = cont(params)
+        per_instance = 1 if params.ndim == 4 else 0
+        params = params.reshape((self.B, -1, P.nb, 10) if per_instance else (-1, P.nb, 10))
+        return (params.shape[1] if per_instance else params.shape[0]), per_instance, params
+
+    def friction_margin(self, x, params, kappa_max=8.0, want_lo=False, want_z=False, want_y=False, want_iters=False):
+        """kappa* (n, n_scen): the friction margin of the robot states x (n, 3 nq) under the inertial parameters params (layouts of
+        balance_check) -- the smallest common scale on the arrangement's friction coefficients at which balancing forces exist
+        (upr_batch_friction_margin_points).  kappa* < 1: the state is balanced and 1 - kappa* of the friction could be lost;
+        kappa* > 1: this much more friction would have been needed; kappa* = 0: normal forces alone balance the state; inf: no
+        friction up to kappa_max times the arrangement's helps (tipping, lift-off).  The smallest friction coefficient of contact i
+        that keeps the state balanced is kappa* mu_i (mu_i = problem.contact_mu, the margin already subtracted).  The force bounds
+        u_lb / u_ub are not part of it.  kappa* carries the rule of the search: a state counts as balanced at a scale when the
+        distance rho there is <= 1e-8 max(|b|, 1), the precision the controller enforces the constraint to, so kappa* lies below
+        the exact boundary by what that ball allows (about 1e-8 at the arrangements of the study), and it is the upper end of a
+        bracket of width kappa_max 2^-32.
+
+        Returns kappa* alone or the tuple (kappa*, kappa_lo, z, y, iters) restricted to what was asked for: kappa_lo (n, n_scen) the
+        last infeasible scale; z (n, n_scen, ncol) >= 0 the generator multipliers at kappa* with |b + A(kappa*) z| inside the ball;
+        y (n, n_scen, 6 nb) the residual at kappa_lo, a separating direction (y' a_j(kappa_lo) >= 0 for every generator, y' b > 0);
+        iters (n, n_scen) the least-squares solves over all evaluations."""
+        P = self.problem
+        x = cont(x).reshape(-1, self.nx)
+        n = x.shape[0]
+        params = cont(params)
+        per_point = params.ndim == 4
+        params = params.reshape((n, -1, P.nb, 10) if per_point else (-1, P.nb, 10))
+        n_scen = params.shape[1] if per_point else params.shape[0]
+        hi = np.zeros((n, n_scen))
+        lo = np.zeros((n, n_scen)) if want_lo else None
+        z = np.zeros((n, n_scen, self.balance_columns)) if want_z else None
+        y = np.zeros((n, n_scen, 6 * P.nb)) if want_y else None
+        iters = np.zeros((n, n_scen), dtype=np.int32) if want_iters else None
+        check(self._lib.upr_batch_friction_margin_points(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, float(kappa_max),
+                                                         ptr(hi), ptr(lo), ptr(z), ptr(y), iptr(iters)))
+        out = (hi,) + tuple(a for a in (lo, z, y, iters) if a is not None)
+        return out[0] if len(out) == 1 else out
+
+    def friction_margin_plan(self, params=None, kappa_max=8.0, want_lo=False, want_iters=False):
+        """kappa* (B, N + 1, n_scen) at the knots of the current plan, evaluated where they lie on the device
+        (upr_batch_friction_margin_plan); params as in balance_check_plan, the quantity as in friction_margin.  With want_lo /
+        want_iters the tuple (kappa*, kappa_lo, iters) restricted to what was asked for."""
+        n_scen, per_instance, params = self._plan_params(params)
+        shape = (self.B, self.N + 1, n_scen)
+        hi = np.zeros(shape)
+        lo = np.zeros(shape) if want_lo else None
+        iters = np.zeros(shape, dtype=np.int32) if want_iters else None
+        check(self._lib.upr_batch_friction_margin_plan(self._h, n_scen, ptr(params), per_instance, float(kappa_max), ptr(hi), ptr(lo), iptr(iters)))
+        out = (hi,) + tuple(a for a in (lo, iters) if a is not None)
+        return out[0] if len(out) == 1 else out
+
     def balance_ms(self):
-        """Device time (ms) of the kernel launches of the last balance check (HIP events around them)."""
+        """Device time (ms) of the kernel launches of the last balance check or friction margin (HIP events around them)."""
         return float(self._lib.upr_batch_balance_ms(self._h))
 
     def balance_forces(self, z):
