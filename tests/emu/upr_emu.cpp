@@ -16,6 +16,7 @@
 #include "../../upright_amd/csrc/upr_qp3.h"
 #include "../../upright_amd/csrc/upr_qp3_list.h"
 #include "../../upright_amd/csrc/upr_qp_select.h"
+#include "../../upright_amd/csrc/upr_launch_select.h"
 
 template <int NQ, bool ORI>
 static void lin_all_o(const upr_lin_args& A);
@@ -23,7 +24,9 @@ static void lin_all_o(const upr_lin_args& A);
 static int g_lin_form = 1;
 template <int NQ>
 static void lin_all(const upr_lin_args& A) {
-    if (g_lin_form && upr_lin2_eligible(A)) {
+    upr_lin_knobs k;
+    k.lin2 = g_lin_form != 0;
+    if (upr_lin_plan(*A.P, A.d, k).kind == 2 && A.Df) {   // (UPR_EMU_LIN_WRENCH hands no Df over: the phases' wrench-sum form)
         std::vector<double> sh(upr_lin2_layout(A.d, A.P->n_sph).per + 8);
         for (int p = 0; p < A.npoints; ++p) upr_lin2_knot<NQ>(A, upr_lin_locate(A, p), sh.data());
         return;
@@ -241,6 +244,36 @@ void emu_qp_select(const upr_problem* P, const upr_qp_knobs* k, int* out, char* 
     std::copy(v, v + 23, out);
     out[23] = s.fb_fused;
     std::copy(s.name, s.name + sizeof(s.name), name);
+}
+
+// The linearisation record of upr_launch_select.h for P under the knobs k, as upr_batch_create plans it, and its name at a launch
+// of npoints knots.  out[0..9] = kind, NQ, USE_MFMA, OCC, ORI, NPASS, knots per workgroup, LDS bytes, too_large, workgroups
+void emu_lin_select(const upr_problem* P, const upr_lin_knobs* k, int npoints, int* out, char* name) {
+    const upr_lin_choice s = upr_lin_plan(*P, upr_make_dims(P), *k);
+    const int blocks = (npoints + s.kpw - 1) / s.kpw;
+    const int v[10] = {s.kind, s.nq, s.mfma, s.occ, s.ori, s.npass, s.kpw, (int)s.lds, s.too_large, blocks};
+    std::copy(v, v + 10, out);
+    upr_lin_name(s, blocks, name, 128);
+}
+// ... and the line-search record: out[0..6] = NQ, NFM, NBM, EXACT, OBS, STAGE, LDS bytes
+void emu_ls_select(const upr_problem* P, const upr_ls_knobs* k, int* out, char* name) {
+    const upr_ls_choice s = upr_ls_plan(*P, upr_make_dims(P), *k);
+    const int v[7] = {s.nq, s.nfm, s.nbm, s.exact, s.obs, s.stage, (int)s.lds};
+    std::copy(v, v + 7, out);
+    upr_ls_name(s, name, 128);
+}
+// the lists themselves, four ints per entry: UPR_LIN_FORMS (USE_MFMA, OCC, ORI, NPASS) and UPR_LS_FORMS (NFM, NBM, EXACT, OBS); returns the entries
+int emu_lin_forms(int* out) {
+    int n = 0;
+#define EMU_X(a, b, c, e) { const int t[4] = {a, b, c, e}; std::copy(t, t + 4, out + 4 * n++); }
+    UPR_LIN_FORMS(EMU_X)
+    return n;
+}
+int emu_ls_forms(int* out) {
+    int n = 0;
+    UPR_LS_FORMS(EMU_X)
+#undef EMU_X
+    return n;
 }
 
 long emu_qp3_lds_doubles() { return (long)upr_qp3_lds<upr_qp3_cfg<9, 1, 4, 3, 20, 256>>::total; }

@@ -659,64 +659,51 @@ def test_every_qp_instantiation_has_a_screen_case():
         need = E.emu_qp3_cfg_fb((C.c_int * 8)(*[int(v) for v in t]), None, 1, None, None, None, None, None, None, C.c_long(0), None, None, None, C.c_long(0))
         assert need > 0, (t, need)
     assert E.emu_qp3_cfg_fb((C.c_int * 8)(9, 1, 4, 3, 21, 0, 0, 0), None, 1, None, None, None, None, None, None, C.c_long(0), None, None, None, C.c_long(0)) == -1
-    # ... and the line-search table of tests/test_gpu_linesearch.py reaches all four forms of launch_linesearch
+    # ... and the line-search table of tests/test_gpu_linesearch.py reaches all four forms of the list (upr_launch_select.h, UPR_LS_FORMS)
     from test_gpu_linesearch import DEVICE_CASES, GOLDEN_LS
-    from test_ls_reference import EXACT, EXACT_ROWS, LARGE, SMALL, ls_case
+    from test_ls_reference import EXACT, EXACT_ROWS, LARGE, LS_FORMS, SMALL, ls_case
     import json
     arr = json.load(open(Path(__file__).resolve().parent / "golden" / "arrangements.json"))
     forms = {GOLDEN_LS[n][1] if n in GOLDEN_LS else ls_case(arr, n)["form"] for n in DEVICE_CASES}
     assert forms == {EXACT, EXACT_ROWS, SMALL, LARGE}, forms
+    listed = _listed_forms(E.emu_ls_forms)
+    assert len(listed) == 4 and {LS_FORMS[f] for f in forms} == set(listed), (forms, listed)
 
 
-def _launch_linearize_forms():
-    """Every kernel instantiation launch_linearize (upr_api.hip) names, at both chain lengths, in the form notation of
-    tests/test_gpu_lin_screen.py: ("lin2", NQ) and ("lin", NQ, USE_MFMA, OCC, ORI, NPASS) with the template's defaults
-    (upr_linearize.h: OCC = 2, ORI = false, NPASS = 1) and UPR_LIN_PASSES filled in."""
-    import re
-    csrc = Path(__file__).resolve().parents[1] / "upright_amd" / "csrc"
-    text = (csrc / "upr_api.hip").read_text()
-    body = text.split("int launch_linearize(upr_batch* h, const upr_lin_args& A) {", 1)[1].split("\ntypedef int (*upr_qp_launcher)", 1)[0]
-    header = (csrc / "upr_linearize.h").read_text()
-    passes = int(re.search(r"#define\s+UPR_LIN_PASSES\s+(\d+)", header).group(1))
-    assert re.search(r"template <int NQ, bool USE_MFMA, int OCC = 2, bool ORI = false, int NPASS = 1>\s*__global__ void __launch_bounds__\(256, OCC\) upr_linearize_kernel", header)
-    flag = {"true": True, "false": False}
-    forms, sites = set(), 0
-    for name, args in re.findall(r"\b(upr_linearize2?_kernel)<([^>]*)>", body):
-        a = [w.strip() for w in args.split(",")]
-        assert a[0] == "NQ", (name, args)
-        sites += 1
-        for nq in (6, 9):
-            if name == "upr_linearize2_kernel":
-                assert len(a) == 1
-                forms.add(("lin2", nq))
-            else:
-                t = a[1:] + ["2", "false", "1"][len(a) - 2:]
-                forms.add(("lin", nq, flag[t[0]], int(t[1]), flag[t[2]], passes if t[3] == "UPR_LIN_PASSES" else int(t[3])))
-    assert re.search(r"\(h->P\.nq == 6\) \? launch_linearize<6>\(h, A\) : launch_linearize<9>\(h, A\)", text)
-    return forms, sites
+def _listed_forms(f):
+    """An instantiation list of upr_launch_select.h as the emulation writes it out (emu_lin_forms: (USE_MFMA, OCC, ORI, NPASS);
+    emu_ls_forms: (NFM, NBM, EXACT, OBS)), in list order; the flags as bool"""
+    out = (C.c_int * 64)()
+    n = f(out)
+    rows = [tuple(out[4 * i:4 * i + 4]) for i in range(n)]
+    if f.__name__ == "emu_lin_forms":
+        return [(bool(r[0]), r[1], bool(r[2]), r[3]) for r in rows]
+    return [(r[0], r[1], bool(r[2]), bool(r[3])) for r in rows]
 
 
 def test_every_linearisation_form_has_a_screen_case():
-    """Coverage guard of tests/test_gpu_lin_screen.py: every kernel instantiation launch_linearize can pick, at NQ 6 and 9, is the
-    form of a case of the screen's table, the table names no form the launcher lacks, and the cases the screen was specified with
-    are all there -- an instantiation added to the launcher, or a case deleted from the table, fails here before any GPU time."""
+    """Coverage guard of tests/test_gpu_lin_screen.py: every kernel instantiation of the list upr_batch_create resolves a plan with
+    (upr_launch_select.h: UPR_LIN_FORMS and upr_linearize2_kernel), at NQ 6 and 9, is the form of a case of the screen's table, the
+    table names no form the list lacks, and the cases the screen was specified with are all there -- an instantiation added to the
+    list, or a case deleted from the table, fails here before any GPU time."""
     import sys
     sys.path.insert(0, str(Path(__file__).resolve().parent))
     from test_gpu_lin_screen import CASES, KNOBS
 
-    forms, sites = _launch_linearize_forms()
-    assert sites == 10 and len(forms) == 18, (sites, sorted(forms))   # upr_linearize2_kernel + nine launches of eight instantiations
+    listed = _listed_forms(C.CDLL(str(EMU)).emu_lin_forms)
+    forms = {("lin2", nq) for nq in (6, 9)} | {("lin", nq) + f for nq in (6, 9) for f in listed}
+    assert len(listed) == 8 and len(forms) == 18, (listed, sorted(forms))   # upr_linearize2_kernel + eight instantiations, at both chain lengths
     table = {tuple(v[3]) for v in CASES.values()}
     assert not forms - table, "instantiations without a screen case: %s" % sorted(forms - table)
-    assert not table - forms, "cases whose form launch_linearize does not have: %s" % sorted(table - forms)
+    assert not table - forms, "cases whose form the list does not have: %s" % sorted(table - forms)
     required = ["headline_B37", "headline_B1024", "ur10_demo", "arm_only", "robust_N20", "robust_N100", "cups", "dice", "box_arch_rows",
                 "collision_rows", "thrown_ball", "two_obstacles", "box_only", "box_collision_rows", "orientation", "orientation_ur10",
                 "orientation_box", "headline_lin2_off", "collision_rows_lin2_off", "headline_no_mfma", "orientation_no_mfma"]
     assert not [n for n in required if n not in CASES], [n for n in required if n not in CASES]
-    # the process-static knobs: both values of each, two cases per value, one at each chain length
+    # the A/B knobs: both values of each, two cases per value, one at each chain length
     assert KNOBS == [("UPR_LIN_OCC", "3"), ("UPR_LIN_OCC", "4"), ("UPR_LIN_ROW_PASSES", "1"), ("UPR_LIN_ROW_PASSES", "3")]
     for knob in KNOBS:
-        assert sorted(v[3][1] for v in CASES.values() if v[4] == knob) == [6, 9], knob
+        assert sorted(v[3][1] for v in CASES.values() if v[2].get(knob[0]) == knob[1]) == [6, 9], knob
     # the row-pass forms are reached by a shape with collision rows, the multi-pass form by one without (same instantiation at 3 passes)
     for nq in (6, 9):
         with_rows = {bool(v[1].get("rows")) for v in CASES.values() if tuple(v[3]) == ("lin", nq, True, 2, False, 3)}
@@ -849,3 +836,145 @@ def test_qp_selection_record(monkeypatch):
             print("%s: %s" % (knob, r))
             assert (r["structure"], r["name"]) == (structure, name) and not r["fb_fused"], (knob, r)
             check_sizes(P, r)
+
+
+class _LinKnobs(C.Structure):
+    """upr_lin_knobs of upr_launch_select.h"""
+    _fields_ = [("mfma", C.c_bool), ("lin2", C.c_bool), ("occ", C.c_int), ("row_passes", C.c_int)]
+
+
+class _LsKnobs(C.Structure):
+    """upr_ls_knobs of upr_launch_select.h"""
+    _fields_ = [("stage_full", C.c_int)]
+
+
+def _lin_knobs(env):
+    """The environment at upr_batch_create as the knobs it reads from it (the defaults: an empty environment's)"""
+    return _LinKnobs(mfma=int(env.get("UPR_LIN_MFMA", 1)) != 0, lin2=int(env.get("UPR_LIN2", 1)) != 0, occ=int(env.get("UPR_LIN_OCC", 2)),
+                     row_passes=int(env.get("UPR_LIN_ROW_PASSES", 2)))
+
+
+def _lin_select(E, P, knobs, npoints):
+    """The linearisation record for P under the knobs (emu_lin_select) at a launch of npoints knots, as a dict"""
+    out = (C.c_int * 10)()
+    name = C.create_string_buffer(128)
+    cp = _capi.problem_to_c(P)
+    E.emu_lin_select(C.byref(cp), C.byref(knobs), npoints, out, name)
+    r = dict(zip(("kind", "nq", "mfma", "occ", "ori", "npass", "kpw", "lds", "too_large", "blocks"), out), name=name.value.decode())
+    r["form"] = ("lin2", r["nq"]) if r["kind"] == 2 else ("lin", r["nq"], bool(r["mfma"]), r["occ"], bool(r["ori"]), r["npass"])
+    return r
+
+
+def _ls_select(E, P, stage_full=-1):
+    """The line-search record for P (emu_ls_select), as a dict; form: (NQ, NFM, NBM, EXACT, OBS)"""
+    out = (C.c_int * 7)()
+    name = C.create_string_buffer(128)
+    cp = _capi.problem_to_c(P)
+    E.emu_ls_select(C.byref(cp), C.byref(_LsKnobs(stage_full=stage_full)), out, name)
+    v = list(out)
+    return dict(form=(v[0], v[1], v[2], bool(v[3]), bool(v[4])), stage=bool(v[5]), lds=v[6], name=name.value.decode())
+
+
+# What the launchers of the PARENT of the commit that introduced upr_launch_select.h computed: their own expressions for the knots
+# per workgroup, the LDS bytes, the workgroups and the staging, evaluated by a host program against that commit's headers, and the
+# names its upr_batch_lin_kernel_name / upr_batch_ls_kernel_name printed.  (case of test_gpu_lin_screen.CASES, environment at create,
+# knots of the trajectory-mode launch) -> (kind, knots per workgroup, LDS bytes, workgroups, name)
+PARENT_LIN = {
+    ("headline_B37", "", 777): (2, 28, 49360, 28, "upr_linearize2_kernel<9> kpw=28 blocks=28"),
+    ("headline_B1024", "", 21504): (2, 28, 49360, 768, "upr_linearize2_kernel<9> kpw=28 blocks=768"),
+    ("collision_rows", "", 84): (2, 28, 53664, 3, "upr_linearize2_kernel<9> kpw=28 blocks=3"),
+    ("collision_rows", "UPR_LIN2=0", 84): (1, 16, 69112, 6, "upr_linearize_kernel<9, true, 2, false, 2>"),
+    ("orientation", "", 63): (1, 8, 31992, 8, "upr_linearize_kernel<9, true, 2, true, 1>"),
+    ("ur10_demo", "", 63): (2, 42, 51712, 2, "upr_linearize2_kernel<6> kpw=42 blocks=2"),
+    ("dice", "", 63): (2, 28, 50704, 3, "upr_linearize2_kernel<9> kpw=28 blocks=3"),
+    ("robust_N100", "", 404): (2, 25, 52648, 17, "upr_linearize2_kernel<9> kpw=25 blocks=17"),
+}
+# case of test_gpu_linesearch.LS_CASES ("orientation": of test_ls_reference.ls_case) -> (LDS bytes, STAGE, name)
+PARENT_LS = {
+    "headline": (39000, True, "upr_linesearch_kernel<9, 128, 12, 1, true, false, true>"),
+    "collision_rows": (39000, True, "upr_linesearch_kernel<9, 128, 12, 1, true, true, true>"),
+    "orientation": (39000, True, "upr_linesearch_kernel<9, 128, 12, 1, true, false, true>"),
+    "ur10_demo": (28184, True, "upr_linesearch_kernel<6, 128, 12, 1, false, true, true>"),
+    "dice": (25128, False, "upr_linesearch_kernel<9, 128, 96, 8, false, true, false>"),
+    "robust_N100": (83368, False, "upr_linesearch_kernel<9, 128, 96, 8, false, true, false>"),
+}
+
+
+def test_lin_and_ls_selection_record(monkeypatch, arrangements):
+    """The plans of upr_launch_select.h -- the rules upr_batch_create resolves a handle's linearisation and line-search kernels with --
+    on the host: every case of the two GPU screens' tables gets the form its table names (the headline 28 knots per workgroup: 28
+    and 768 workgroups), no knob combination leads outside the lists the kernels are instantiated from, and knots per workgroup, LDS
+    bytes, staging and names equal what the launchers computed before the rules were moved here (PARENT_LIN, PARENT_LS)."""
+    import sys
+    sys.path.insert(0, str(Path(__file__).resolve().parent))
+    import test_gpu_lin_screen as S
+    import test_gpu_linesearch as L
+    from test_ls_reference import LS_FORMS, ls_case
+    from upright_amd import control_bindings
+
+    monkeypatch.setattr(control_bindings, "BatchMPC", _NoDevice)   # (the builders keep the manager's Problem and close its handle)
+    E = C.CDLL(str(EMU))
+    built = {}
+
+    def lin_case(name):     # (P, knots of the trajectory-mode launch); cases that differ only in the launch form share their inputs
+        key = (S.CASES[name][0].__name__, tuple(sorted(S.CASES[name][1].items())))
+        if key not in built:
+            c = S.build_case(name)
+            built[key] = (c["P"], c["xs"].shape[0] * (c["P"].N + 1))
+        return built[key]
+
+    # 1. the linearisation screen's table
+    for name, (_, _, env, form) in S.CASES.items():
+        P, npoints = lin_case(name)
+        r = _lin_select(E, P, _lin_knobs(env), npoints)
+        print(name, env, npoints, r)
+        assert r["form"] == tuple(form) and not r["too_large"], (name, r)
+        ran, kpw, blocks = S.parse_lin_kernel(r["name"])
+        assert ran == tuple(form) and r["blocks"] == -(-npoints // r["kpw"]), (name, r)
+        if r["kind"] == 2:
+            assert (kpw, blocks) == (r["kpw"], r["blocks"]) and 1 <= kpw <= 256 // P.nq, (name, r)
+        else:
+            assert r["kpw"] == 8 * r["npass"], (name, r)
+        if name in S.KPW:
+            assert (r["kpw"], r["blocks"]) == S.KPW[name] and r["kpw"] == 28 and npoints == {"headline_B37": 777, "headline_B1024": 21504}[name], (name, r)
+        pin = PARENT_LIN.get((name, ",".join("%s=%s" % kv for kv in sorted(env.items())), npoints))
+        if pin:
+            assert (r["kind"], r["kpw"], r["lds"], r["blocks"], r["name"]) == pin, (name, r, pin)
+    assert all(any(k[:2] == (n, e) for k in PARENT_LIN) for n, e in
+               [("headline_B37", ""), ("headline_B1024", ""), ("collision_rows", ""), ("collision_rows", "UPR_LIN2=0"), ("orientation", ""), ("ur10_demo", ""), ("dice", ""), ("robust_N100", "")])
+
+    # 2. the line-search tables
+    ls_seen = {}
+    for name, (builder, kw, form, stage) in L.LS_CASES.items():
+        r = ls_seen[name] = _ls_select(E, builder(**kw)["P"])
+        print(name, r)
+        assert r["form"] == form and r["name"] == L._name(*form, r["stage"]) and (stage is None or r["stage"] == stage), (name, r)
+    for name in L.DEVICE_CASES:
+        c = L._golden_ls(L.GOLDEN_LS[name][0], L.GOLDEN_LS[name][1], **L.GOLDEN_LS[name][2]) if name in L.GOLDEN_LS else ls_case(arrangements, name)
+        r = _ls_select(E, c["P"])
+        print(name, r)
+        assert r["form"] == (c["P"].nq,) + LS_FORMS[c["form"]], (name, r)
+        if name == "orientation":
+            ls_seen[name] = r
+    assert not ls_seen["robust_N100"]["stage"] and not _ls_select(E, ls_case(arrangements, "robust_N100")["P"])["stage"]
+    assert set(PARENT_LS) <= set(ls_seen)
+    for name, pin in PARENT_LS.items():
+        r = ls_seen[name]
+        assert (r["lds"], r["stage"], r["name"]) == pin, (name, r, pin)
+
+    # 3. the whole knob grid on one shape of each class: always a member of the lists
+    lin_forms, ls_forms = _listed_forms(E.emu_lin_forms), _listed_forms(E.emu_ls_forms)
+    shapes = {"headline": "headline_B37", "collision rows": "collision_rows", "orientation cost": "orientation", "nq 6": "ur10_demo", "multi-body": "robust_N20"}
+    for cls, name in shapes.items():
+        P, npoints = lin_case(name)
+        assert {"headline": (P.nq, P.nb, P.nc, P.N) == (9, 1, 4, 20) and not P.n_state_rows, "collision rows": P.n_state_rows > 0,
+                "orientation cost": bool(np.any(np.asarray(P.Wee)[3:] != 0)), "nq 6": P.nq == 6, "multi-body": P.nb > 1}[cls], (cls, name)
+        for mfma in (False, True):
+            for lin2 in (False, True):
+                for occ in (2, 3, 4):
+                    for passes in (1, 2, 3):
+                        r = _lin_select(E, P, _LinKnobs(mfma=mfma, lin2=lin2, occ=occ, row_passes=passes), npoints)
+                        assert r["nq"] == P.nq and (r["kind"] == 2 or (r["kind"] == 1 and r["form"][2:] in lin_forms)), (cls, mfma, lin2, occ, passes, r)
+        for stage_full in (-1, 0, 1):
+            r = _ls_select(E, P, stage_full)
+            assert r["form"][0] == P.nq and r["form"][1:] in ls_forms, (cls, stage_full, r)

@@ -1,20 +1,18 @@
-"""Screen of every launch form of the linearisation (upr_api.hip, launch_linearize): whole records, in trajectory mode (what
+"""Screen of every launch form of the linearisation (upr_launch_select.h, upr_lin_plan): whole records, in trajectory mode (what
 advance, qp_step and tick launch: knot, instance and time come from the point index, the terminal record is its own, dynamic
 obstacles are predicted from the observation) and in points mode, against the numpy statement of tests/lin_check.py on the
 oracle's terms, at the project's own tolerances (lin_check.TOL).  kernel_times()["lin_kernel"] names the instantiation the launch
-ran; the last test asserts that the table reached every instantiation launch_linearize can pick, at both chain lengths.
+ran; the last test asserts that the table reached every instantiation the plan can pick, at both chain lengths.
 
-CASES maps a case to (builder, builder kwargs, environment of the handle, form the launch must pick, process-static knob or
-None).  A form is ("lin2", NQ) or ("lin", NQ, USE_MFMA, OCC, ORI, NPASS).  The builders give every instance its own inertial
+CASES maps a case to (builder, builder kwargs, environment at upr_batch_create, form the launch must pick).  A form is
+("lin2", NQ) or ("lin", NQ, USE_MFMA, OCC, ORI, NPASS).  The builders give every instance its own inertial
 parameters, targets and non-zero time, a trajectory in motion and (where there is one) its own obstacle and projectile flag, so
 that every piece of addressing can fail visibly.  tests/test_lin_reference.py runs the same table through the host emulation;
-tests/test_emu.py (test_every_linearisation_form_has_a_screen_case) fails the CPU suite when launch_linearize gains an
-instantiation without a case here.  Cases behind a process-static knob (UPR_LIN_OCC, UPR_LIN_ROW_PASSES: read once per process)
-run in a fresh child process each."""
+tests/test_emu.py (test_every_linearisation_form_has_a_screen_case) fails the CPU suite when the list of instantiations gains
+one without a case here, and test_lin_and_ls_selection_record holds the plan to the forms of this table on the host."""
 import json
 import os
 import re
-import subprocess
 import sys
 import time
 from pathlib import Path
@@ -23,7 +21,6 @@ import numpy as np
 import pytest
 
 HERE = Path(__file__).resolve().parent
-ROOT = HERE.parent
 sys.path.insert(0, str(HERE))
 
 import lin_check  # noqa: E402
@@ -164,48 +161,49 @@ def _two_obstacles():
 
 
 LIN2_OFF, NO_MFMA = {"UPR_LIN2": "0"}, {"UPR_LIN_MFMA": "0"}
+OCC3, OCC4 = {"UPR_LIN_OCC": "3"}, {"UPR_LIN_OCC": "4"}
+PASSES1, PASSES3 = dict(LIN2_OFF, UPR_LIN_ROW_PASSES="1"), dict(LIN2_OFF, UPR_LIN_ROW_PASSES="3")
 ARM, UR10 = {"name": "full_bottle_arm_only"}, {"name": "ur10_demo"}
-# case -> (builder, kwargs, environment at upr_batch_create, form, process-static knob (name, value) or None)
+# case -> (builder, kwargs, environment at upr_batch_create, form)
 CASES = {
-    "headline_B37": (_thing, {"B": 37}, {}, ("lin2", 9), None),          # 777 knots: 27 workgroups of 28 and one of 21
-    "headline_B1024": (_thing, {"B": 1024}, {}, ("lin2", 9), None),      # 768 workgroups, the launch the bench times
-    "ur10_demo": (_golden, UR10, {}, ("lin2", 6), None),                 # nq 6, nf 1
-    "arm_only": (_golden, ARM, {}, ("lin2", 6), None),                   # nq 6, nf 3
-    "robust_N20": (_robust, {}, {}, ("lin2", 9), None),
-    "robust_N100": (_robust, {"N": 100}, {}, ("lin2", 9), None),
-    "cups": (_thing, {"arr": "blue_cups"}, {}, ("lin2", 9), None),
-    "dice": (_thing, {"arr": "foam_die2"}, {}, ("lin2", 9), None),
-    "box_arch_rows": (_thing, {"arr": "box_arch", "rows": "simple", "B": 4}, {}, ("lin2", 9), None),
-    "collision_rows": (_thing, {"rows": "small", "B": 4}, {}, ("lin2", 9), None),
-    "ur10_collision_rows": (_golden, dict(UR10, rows=True), {}, ("lin2", 6), None),
-    "thrown_ball": (_thrown_ball, {}, {}, ("lin2", 9), None),
-    "two_obstacles": (_two_obstacles, {}, {}, ("lin2", 9), None),
-    "box_only": (_thing, {"box": True, "two": True}, {}, ("lin2", 9), None),
-    "box_collision_rows": (_thing, {"rows": "small", "box": True, "B": 4}, {}, ("lin2", 9), None),
-    "orientation": (_thing, {"ori": True}, {}, ("lin", 9, True, 2, True, 1), None),
-    "orientation_ur10": (_golden, dict(UR10, ori=True), {}, ("lin", 6, True, 2, True, 1), None),
-    "orientation_box": (_thing, {"ori": True, "box": True}, {}, ("lin", 9, True, 2, True, 1), None),
+    "headline_B37": (_thing, {"B": 37}, {}, ("lin2", 9)),          # 777 knots: 27 workgroups of 28 and one of 21
+    "headline_B1024": (_thing, {"B": 1024}, {}, ("lin2", 9)),      # 768 workgroups, the launch the bench times
+    "ur10_demo": (_golden, UR10, {}, ("lin2", 6)),                 # nq 6, nf 1
+    "arm_only": (_golden, ARM, {}, ("lin2", 6)),                   # nq 6, nf 3
+    "robust_N20": (_robust, {}, {}, ("lin2", 9)),
+    "robust_N100": (_robust, {"N": 100}, {}, ("lin2", 9)),
+    "cups": (_thing, {"arr": "blue_cups"}, {}, ("lin2", 9)),
+    "dice": (_thing, {"arr": "foam_die2"}, {}, ("lin2", 9)),
+    "box_arch_rows": (_thing, {"arr": "box_arch", "rows": "simple", "B": 4}, {}, ("lin2", 9)),
+    "collision_rows": (_thing, {"rows": "small", "B": 4}, {}, ("lin2", 9)),
+    "ur10_collision_rows": (_golden, dict(UR10, rows=True), {}, ("lin2", 6)),
+    "thrown_ball": (_thrown_ball, {}, {}, ("lin2", 9)),
+    "two_obstacles": (_two_obstacles, {}, {}, ("lin2", 9)),
+    "box_only": (_thing, {"box": True, "two": True}, {}, ("lin2", 9)),
+    "box_collision_rows": (_thing, {"rows": "small", "box": True, "B": 4}, {}, ("lin2", 9)),
+    "orientation": (_thing, {"ori": True}, {}, ("lin", 9, True, 2, True, 1)),
+    "orientation_ur10": (_golden, dict(UR10, ori=True), {}, ("lin", 6, True, 2, True, 1)),
+    "orientation_box": (_thing, {"ori": True, "box": True}, {}, ("lin", 9, True, 2, True, 1)),
     # forms chosen per handle
-    "headline_lin2_off": (_thing, {"B": 37}, LIN2_OFF, ("lin", 9, True, 2, False, 3), None),
-    "collision_rows_lin2_off": (_thing, {"rows": "small", "B": 4}, LIN2_OFF, ("lin", 9, True, 2, False, 2), None),
-    "arm_only_lin2_off": (_golden, ARM, LIN2_OFF, ("lin", 6, True, 2, False, 3), None),
-    "ur10_collision_rows_lin2_off": (_golden, dict(UR10, rows=True), LIN2_OFF, ("lin", 6, True, 2, False, 2), None),
-    "headline_no_mfma": (_thing, {"B": 5}, NO_MFMA, ("lin", 9, False, 2, False, 1), None),
-    "arm_only_no_mfma": (_golden, ARM, NO_MFMA, ("lin", 6, False, 2, False, 1), None),
-    "orientation_no_mfma": (_thing, {"ori": True}, NO_MFMA, ("lin", 9, False, 2, True, 1), None),
-    "orientation_ur10_no_mfma": (_golden, dict(UR10, ori=True), NO_MFMA, ("lin", 6, False, 2, True, 1), None),
-    # forms behind process-static knobs: a fresh child process per knob value, two small cases each
-    "headline_occ3": (_thing, {"B": 5}, {}, ("lin", 9, True, 3, False, 1), ("UPR_LIN_OCC", "3")),
-    "arm_only_occ3": (_golden, ARM, {}, ("lin", 6, True, 3, False, 1), ("UPR_LIN_OCC", "3")),
-    "headline_occ4": (_thing, {"B": 5}, {}, ("lin", 9, True, 4, False, 1), ("UPR_LIN_OCC", "4")),
-    "arm_only_occ4": (_golden, ARM, {}, ("lin", 6, True, 4, False, 1), ("UPR_LIN_OCC", "4")),
-    "collision_rows_passes1": (_thing, {"rows": "small", "B": 4}, LIN2_OFF, ("lin", 9, True, 2, False, 1), ("UPR_LIN_ROW_PASSES", "1")),
-    "ur10_collision_rows_passes1": (_golden, dict(UR10, rows=True), LIN2_OFF, ("lin", 6, True, 2, False, 1), ("UPR_LIN_ROW_PASSES", "1")),
-    "collision_rows_passes3": (_thing, {"rows": "small", "B": 4}, LIN2_OFF, ("lin", 9, True, 2, False, 3), ("UPR_LIN_ROW_PASSES", "3")),
-    "ur10_collision_rows_passes3": (_golden, dict(UR10, rows=True), LIN2_OFF, ("lin", 6, True, 2, False, 3), ("UPR_LIN_ROW_PASSES", "3")),
+    "headline_lin2_off": (_thing, {"B": 37}, LIN2_OFF, ("lin", 9, True, 2, False, 3)),
+    "collision_rows_lin2_off": (_thing, {"rows": "small", "B": 4}, LIN2_OFF, ("lin", 9, True, 2, False, 2)),
+    "arm_only_lin2_off": (_golden, ARM, LIN2_OFF, ("lin", 6, True, 2, False, 3)),
+    "ur10_collision_rows_lin2_off": (_golden, dict(UR10, rows=True), LIN2_OFF, ("lin", 6, True, 2, False, 2)),
+    "headline_no_mfma": (_thing, {"B": 5}, NO_MFMA, ("lin", 9, False, 2, False, 1)),
+    "arm_only_no_mfma": (_golden, ARM, NO_MFMA, ("lin", 6, False, 2, False, 1)),
+    "orientation_no_mfma": (_thing, {"ori": True}, NO_MFMA, ("lin", 9, False, 2, True, 1)),
+    "orientation_ur10_no_mfma": (_golden, dict(UR10, ori=True), NO_MFMA, ("lin", 6, False, 2, True, 1)),
+    # forms behind the A/B knobs UPR_LIN_OCC and UPR_LIN_ROW_PASSES: two small cases per value
+    "headline_occ3": (_thing, {"B": 5}, OCC3, ("lin", 9, True, 3, False, 1)),
+    "arm_only_occ3": (_golden, ARM, OCC3, ("lin", 6, True, 3, False, 1)),
+    "headline_occ4": (_thing, {"B": 5}, OCC4, ("lin", 9, True, 4, False, 1)),
+    "arm_only_occ4": (_golden, ARM, OCC4, ("lin", 6, True, 4, False, 1)),
+    "collision_rows_passes1": (_thing, {"rows": "small", "B": 4}, PASSES1, ("lin", 9, True, 2, False, 1)),
+    "ur10_collision_rows_passes1": (_golden, dict(UR10, rows=True), PASSES1, ("lin", 6, True, 2, False, 1)),
+    "collision_rows_passes3": (_thing, {"rows": "small", "B": 4}, PASSES3, ("lin", 9, True, 2, False, 3)),
+    "ur10_collision_rows_passes3": (_golden, dict(UR10, rows=True), PASSES3, ("lin", 6, True, 2, False, 3)),
 }
-IN_PROCESS = [n for n, v in CASES.items() if v[4] is None]
-KNOBS = sorted({v[4] for v in CASES.values() if v[4] is not None})
+KNOBS = sorted({(k, v[2][k]) for v in CASES.values() for k in ("UPR_LIN_OCC", "UPR_LIN_ROW_PASSES") if k in v[2]})
 # knots per workgroup of upr_linearize2_kernel: 28 for the headline shape (768 workgroups at B = 1024), 256 / NQ at most
 KPW = {"headline_B37": (28, 28), "headline_B1024": (28, 768)}     # case -> (kpw, workgroups) in trajectory mode
 RAGGED = ("headline_B37", "ur10_demo", "arm_only")                # the last workgroup of the trajectory-mode launch is not full
@@ -333,46 +331,14 @@ def reached():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", IN_PROCESS)
+@pytest.mark.parametrize("name", list(CASES))
 def test_linearisation_records_against_the_oracle(name, reached):
     check_result(name, screen_case(name), reached)
 
 
-CHILD = {"dead": None}     # set to the knob whose child ended by signal, abort or time limit: no further child is started
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("knob", KNOBS, ids=lambda k: "%s=%s" % k)
-def test_forms_behind_process_static_knobs(knob, reached):
-    """UPR_LIN_OCC / UPR_LIN_ROW_PASSES are read once per process: each value in a fresh child process that runs the same checker
-    on its two cases and prints the result as JSON."""
-    assert CHILD["dead"] is None, "the child for %s=%s did not end normally: no further child process started" % CHILD["dead"]
-    names = [n for n, v in CASES.items() if v[4] == knob]
-    env = dict(os.environ)
-    env[knob[0]] = knob[1]
-    env["PYTHONPATH"] = os.pathsep.join([str(ROOT), str(HERE)] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
-    try:
-        p = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child", ",".join(names)], env=env, cwd=str(ROOT),
-                           capture_output=True, text=True, timeout=120)
-    except subprocess.TimeoutExpired:
-        CHILD["dead"] = knob
-        raise
-    if p.returncode != 0:
-        if p.returncode < 0 or p.returncode in (124, 134, 137, 139):
-            CHILD["dead"] = knob
-        raise AssertionError("child %s=%s ended with %d:\n%s\n%s" % (knob + (p.returncode, p.stdout[-2000:], p.stderr[-2000:])))
-    res = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
-    assert sorted(res) == sorted(names)
-    for n in names:
-        r = res[n]
-        for k in ("traj", "points"):
-            r[k] = {s: tuple(v) for s, v in r[k].items()}
-        check_result(n, r, reached)
-
-
 @pytest.mark.gpu
 def test_the_table_reaches_every_linearisation_instantiation(reached):
-    """Both chain lengths and every instantiation launch_linearize can pick were launched by the cases above."""
+    """Both chain lengths and every instantiation the plan can pick were launched by the cases above."""
     assert set(reached) == set(CASES), "run the whole module: %s" % sorted(set(CASES) - set(reached))
     forms = {parse_lin_kernel(n)[0] for n in reached.values()}
     want = {("lin2", nq) for nq in (6, 9)} | {("lin", nq) + f for nq in (6, 9) for f in (
@@ -380,8 +346,3 @@ def test_the_table_reaches_every_linearisation_instantiation(reached):
         (True, 2, False, 2), (True, 2, False, 1))}
     assert forms == want, (sorted(want - forms), sorted(forms - want))
 
-
-if __name__ == "__main__":
-    if len(sys.argv) == 3 and sys.argv[1] == "--child":
-        out = {n: screen_case(n) for n in sys.argv[2].split(",")}
-        print(json.dumps(out))

@@ -1,4 +1,4 @@
-"""The line-search launch (upr_api.hip, launch_linesearch) picks one of four forms of upr_linesearch_kernel by the contact structure:
+"""The line-search plan (upr_launch_select.h, upr_ls_plan) picks one of four forms of upr_linesearch_kernel by the contact structure:
 EXACT without rows (the headline's one body on four frictional contacts), EXACT with state rows (collision / projectile rows, the
 end-effector box), the small general form (one body, up to twelve force components) and the large form, each staged or not by its
 LDS footprint.  kernel_times()["ls_kernel"] names the one the handle's last line search ran.
@@ -8,6 +8,8 @@ step length, cost, violation, step norms, the iterate afterwards and the converg
 import sys
 from pathlib import Path
 
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -15,13 +17,14 @@ from upright_amd.engine import BatchMPC
 
 HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE))
+from test_emu import EMU, _ls_select  # noqa: E402
 from test_gpu_qp_screen import _box_arch, _golden, _headline, _obstacles, _robust  # noqa: E402
-from test_ls_reference import CPU_CASES, EXACT, EXACT_ROWS, LARGE, SMALL, check_against_reference, ls_case  # noqa: E402
+from test_ls_reference import CPU_CASES, EXACT, LS_FORMS, SMALL, check_against_reference, ls_case  # noqa: E402
 from upright_amd.sampling import stationary_guess  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-# case -> (builder, kwargs, (NQ, NFM, NBM, EXACT, OBS) of the form launch_linesearch must pick, STAGE or None: by the LDS footprint)
+# case -> (builder, kwargs, (NQ, NFM, NBM, EXACT, OBS) of the form the handle must run, STAGE or None: by the LDS footprint)
 LS_CASES = {
     "headline": (_headline, {"B": 4}, (9, 12, 1, True, False), None),
     "collision_rows": (_obstacles, {}, (9, 12, 1, True, True), None),
@@ -92,7 +95,6 @@ GOLDEN_LS = {
     "arm_only": ("full_bottle_arm_only", EXACT, {}),
 }
 DEVICE_CASES = CPU_CASES + ["robust_N100"] + list(GOLDEN_LS)
-FORM_OF = {EXACT: (True, False), EXACT_ROWS: (True, True), SMALL: (False, True), LARGE: (False, True)}
 BRANCHES = {}
 
 
@@ -130,9 +132,8 @@ def test_line_search_at_the_device_step(arrangements, name):
         done = mpc.stats()["sqp_iters_done"] == 1
     finally:
         mpc.close()
-    exact, obs = FORM_OF[c["form"]]
-    assert ("%d, 128, %s, %s, %s, %s," % (P.nq, "12" if c["form"] != LARGE else "96", "1" if c["form"] != LARGE else "8",
-                                         "true" if exact else "false", "true" if obs else "false")) in ls_name, ls_name
+    plan = _ls_select(C.CDLL(str(EMU)), P)     # (the same rules on the host)
+    assert ls_name == plan["name"] and plan["form"] == (P.nq,) + LS_FORMS[c["form"]], (ls_name, plan, c["form"])
     report, branches = [], []
     for b in range(B):
         r = check_against_reference(c, b, st["step_alpha_last"][b], st["cost"][b], st["constraint_violation"][b], st["dx_norm"][b],

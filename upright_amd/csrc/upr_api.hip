@@ -31,6 +31,7 @@
 #include "upr_qp3_list.h"
 #include "upr_qp3_launch.h"
 #include "upr_qp_select.h"
+#include "upr_launch_select.h"
 #include "upr_value.h"
 #include "upr_balance.h"
 #include "upr_margin.h"
@@ -256,6 +257,16 @@ struct upr_qp_sel : upr_qp_choice {
     upr_fb_src fb{};                 // where the kernel leaves its per-knot factors (kind 0 = no source: the feedback launch is refused)
 };
 
+// ... and its linearisation and line-search kernels (upr_launch_select.h), resolved there too: the record and the kernel it names
+struct upr_lin_sel : upr_lin_choice {
+    const void* kern = nullptr;   // upr_linearize_kernel<...>(A), or upr_linearize2_kernel<NQ>(A, kpw, n_sph) for kind 2
+    char name[128] = "";          // the instantiation with the workgroups of the last launch (upr_batch_lin_kernel_name)
+};
+struct upr_ls_sel : upr_ls_choice {
+    void (*kern)(upr_ls_args) = nullptr;
+    char name[128] = "";          // the instantiation, as rocprofv3 prints it (upr_batch_ls_kernel_name)
+};
+
 struct upr_batch {
     upr_problem P;
     upr_dims d;
@@ -293,8 +304,10 @@ struct upr_batch {
     int sqp_iters_next = 0;   // > 0: SQP iterations of the next advance only (init_sqp_iteration of the first solve)
     double last_ms = 0.0;
     upr_qp_sel qp;   // the QP kernel instantiation this handle launches
-    bool use_mfma = true;
-    bool lin2 = true;   // shapes without collision rows / orientation cost: upr_linearize2_kernel (UPR_LIN2=0 at create: upr_linearize_kernel)
+    upr_lin_sel lin_sel;   // the linearisation kernel instantiation this handle launches
+    upr_ls_sel ls_sel;     // ... and the line-search one
+    int lin_blocks_last = -1;   // workgroups of the last linearisation launch (upr_batch_lin_kernel_name); -1: none yet
+    bool ls_launched = false;   // a line search was launched (upr_batch_ls_kernel_name)
     int timing = 0;   // 0: no events; 1: around every kernel of an advance; 2: around the QP kernel only; 3: around every FOURTH QP launch
     unsigned timing_qp_count = 0;   // QP launches since upr_batch_enable_timing (mode 3 samples those with count % 4 == 0)
     double k_ms[3] = {0, 0, 0};
@@ -319,11 +332,6 @@ struct upr_batch {
     double bal_ms = 0.0;
     void* bal_buf = nullptr; size_t bal_cap = 0;   // scratch of the balance-check calls, grown on demand, used for nothing else
     bool bal_lane = true;   // one-body shapes on the lane-per-job kernel (UPR_BAL_FORM=0 at create: the wave-per-job kernel for them too; tests)
-    std::string ls_name;   // the line-search kernel instantiation of the handle's last line-search launch (upr_batch_ls_kernel_name)
-    int ls_form[5] = {0, 0, 0, 0, -1};   // (NFM, NBM, EXACT, OBS, STAGE) of that launch; STAGE -1: no line search launched yet
-    std::string lin_name;   // the linearisation kernel instantiation of the handle's last linearisation launch (upr_batch_lin_kernel_name)
-    // of that launch: kind (-1: none yet; 1: upr_linearize_kernel; 2: upr_linearize2_kernel), then (USE_MFMA, OCC, ORI, NPASS) or (kpw, blocks)
-    int lin_form[5] = {-1, 0, 0, 0, 0};
     std::vector<hipEvent_t> ev_pool, ev_free;   // events in use (pairs, in launch order) / harvested ones waiting for reuse
     std::vector<int> ev_slot;
 };
@@ -371,61 +379,36 @@ int need_device() {
     return 0;
 }
 
-#ifndef UPR_LIN_ROW_PASSES_DEFAULT
-#define UPR_LIN_ROW_PASSES_DEFAULT 2
-#endif
-template <int NQ>
+// the linearisation kernel of the handle (lin_sel) over A.npoints knots
 int launch_linearize(upr_batch* h, const upr_lin_args& A) {
-    static const int occ = getenv("UPR_LIN_OCC") ? atoi(getenv("UPR_LIN_OCC")) : 2;
-    // knots per workgroup: several passes (their value walks side by side) for the plain instantiation without collision rows
-    // (the end-effector box rows come out of the position Jacobian in the last phase: they leave the layout as it is)
-    const bool multi = UPR_LIN_ANALYTIC && !A.way_q && h->use_mfma && occ == 2 && A.d.nsr == 0;
-    // with collision rows (snapshot form, round 4: 156 instead of 480 doubles of LDS per knot for 16 spheres): UPR_LIN_ROW_PASSES
-    // passes per workgroup (1, 2 or 3)
-    static const int row_passes = getenv("UPR_LIN_ROW_PASSES") ? atoi(getenv("UPR_LIN_ROW_PASSES")) : UPR_LIN_ROW_PASSES_DEFAULT;
-    const bool multi_rows = UPR_LIN_ANALYTIC && UPR_LIN_OBS_SNAP && !A.way_q && h->use_mfma && occ == 2 && A.d.nsr > 0 && (row_passes == 2 || row_passes == 3);
-    // no collision rows, no orientation cost: the one-round kernel of upr_linearize2.h, as many knots per workgroup as three
-    // workgroups per CU hold in LDS and one tangent pass takes in one trip (28 for the headline shape: 768 workgroups)
-    if (h->lin2 && upr_lin2_eligible(A) && h->use_mfma && occ == 2) {
-        const upr_lin2_lay lay = upr_lin2_layout(A.d, h->P.n_sph);
-        const int npre = ((UPR_LIN2_NPRE + 1) & ~1) + (A.d.nsr > 0 ? upr_lin2_table_doubles(h->P.n_sph) : 0);
-        int kpw = (int)((UPR_LIN2_LDS_BUDGET - npre * sizeof(double)) / (lay.per * sizeof(double)));
-        if (kpw > 256 / NQ) kpw = 256 / NQ;
-        if (kpw > 64) kpw = 64;
-        if (kpw >= 1) {
-            const size_t lds2 = (size_t)(npre + kpw * lay.per) * sizeof(double);
-            hipLaunchKernelGGL(upr_linearize2_kernel<NQ>, dim3((A.npoints + kpw - 1) / kpw), dim3(256), lds2, h->stream, A, kpw, h->P.n_sph);
-            h->lin_form[0] = 2; h->lin_form[1] = kpw; h->lin_form[2] = (A.npoints + kpw - 1) / kpw;
-            UPR_HIP(hipGetLastError());
-            return 0;
-        }
-    }
-    const int KPW = 8 * (multi ? UPR_LIN_PASSES : (multi_rows ? row_passes : 1));
-    const int blocks = (A.npoints + KPW - 1) / KPW;
-    const size_t lds = (size_t)KPW * upr_lin_lds_doubles(A.d, h->P.n_sph) * sizeof(double) + sizeof(upr_problem) + 16;   // (+ the kernel's copy of the problem record)
-    if (lds > 160 * 1024) return fail("collision model too large for the linearisation kernel's LDS");
-    // (rounds 1 - 2, one forward-mode walk per tangent lane: 2 -> 0.130 ms, 3 -> 0.142 ms, 4 -> 0.32 ms with spills; round 3, one value
-    // walk per knot + closed-form tangents: 2 -> 0.091 ms, 3 -> 0.085 ms;
-    // with the walks of three passes side by side: 2 -> 0.073 ms, 3 -> 0.095 ms)
-    // (mfma, occ, ori, npass: the template arguments of kern besides NQ, remembered for upr_batch_lin_kernel_name)
-    auto launch = [&](void (*kern)(upr_lin_args), bool mfma, int o, bool ori, int npass) -> int {
-        if (lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, h->stream, A);
-        h->lin_form[0] = 1; h->lin_form[1] = mfma; h->lin_form[2] = o; h->lin_form[3] = ori; h->lin_form[4] = npass;
-        return 0;
-    };
-    int rc;
-    if (A.way_q) rc = h->use_mfma ? launch(upr_linearize_kernel<NQ, true, 2, true>, true, 2, true, 1) : launch(upr_linearize_kernel<NQ, false, 2, true>, false, 2, true, 1);   // end-effector cost with orientation weights
-    else if (!h->use_mfma) rc = launch(upr_linearize_kernel<NQ, false>, false, 2, false, 1);
-    else if (occ == 3) rc = launch(upr_linearize_kernel<NQ, true, 3>, true, 3, false, 1);
-    else if (occ == 4) rc = launch(upr_linearize_kernel<NQ, true, 4>, true, 4, false, 1);
-    else if (multi) rc = launch(upr_linearize_kernel<NQ, true, 2, false, UPR_LIN_PASSES>, true, 2, false, UPR_LIN_PASSES);
-    else if (multi_rows && row_passes == 3) rc = launch(upr_linearize_kernel<NQ, true, 2, false, 3>, true, 2, false, 3);
-    else if (multi_rows) rc = launch(upr_linearize_kernel<NQ, true, 2, false, 2>, true, 2, false, 2);
-    else rc = launch(upr_linearize_kernel<NQ, true>, true, 2, false, 1);
-    if (rc) return rc;
-    UPR_HIP(hipGetLastError());
+    const upr_lin_sel& s = h->lin_sel;
+    if (s.too_large) return fail("collision model too large for the linearisation kernel's LDS");
+    if (s.lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute(s.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
+    const int blocks = (A.npoints + s.kpw - 1) / s.kpw;
+    upr_lin_args Ac = A;
+    int kpw = s.kpw, n_sph = h->P.n_sph;
+    void* args[] = {&Ac, &kpw, &n_sph};   // (a kernel takes as many as it declares: upr_linearize_kernel the first alone)
+    UPR_HIP(hipLaunchKernel(s.kern, dim3(blocks), dim3(256), args, s.lds, h->stream));
+    h->lin_blocks_last = blocks;
     return 0;
+}
+// the instantiation a choice names, at the handle's chain length: the lists of upr_launch_select.h expanded
+template <int NQ>
+const void* lin_kernel(const upr_lin_choice& s) {
+    if (s.kind == 2) return (const void*)upr_linearize2_kernel<NQ>;
+#define X(M, O, R, NP) if (s.mfma == M && s.occ == O && s.ori == R && s.npass == NP) return (const void*)upr_linearize_kernel<NQ, M, O, R, NP>;
+    UPR_LIN_FORMS(X)
+#undef X
+    return nullptr;
+}
+template <int NQ>
+void (*ls_kernel(const upr_ls_choice& s))(upr_ls_args) {
+    // (STAGE is compile-time in the kernel: its staged arrays are LDS pointers, not generic ones)
+#define X(NF, NB, E, O) if (s.nfm == NF && s.nbm == NB && s.exact == E && s.obs == O) \
+        return s.stage ? upr_linesearch_kernel<NQ, 128, NF, NB, E, O, true> : upr_linesearch_kernel<NQ, 128, NF, NB, E, O, false>;
+    UPR_LS_FORMS(X)
+#undef X
+    return nullptr;
 }
 
 typedef int (*upr_qp_launcher)(upr_batch*, const upr_qp_args&);
@@ -684,42 +667,19 @@ int jit_get(const int* tuple, int nt, upr_jit_kernel** out) {
 
 int launch_qp(upr_batch* h, const upr_qp_args& A) { return h->qp.launch(h, A); }
 
-template <int NQ>
+// the line-search kernel of the handle (ls_sel), one workgroup per instance
 int launch_linesearch(upr_batch* h, const upr_ls_args& A0) {
+    const upr_ls_sel& s = h->ls_sel;
     upr_ls_args A = A0;
     A.n_way = h->P.n_way;
     static_assert(3 * UPR_MAX_WAYPOINTS <= 128, "a lane per waypoint coordinate");
-    size_t lds = (size_t)upr_ls_lds_doubles(h->d) * sizeof(double) + sizeof(upr_problem) + 16;   // (+ the kernel's copy of the problem record)
-    // Three staged copies (trajectory, step, trial trajectory) pay for the small shapes only: with one wave per workgroup the LDS
-    // footprint IS the occupancy, and for the large input vectors it costs more than the uncoalesced reads it replaces
-    // (r04, tools/r4_lin.sh: configs[2] 1.58 ms staged / 1.01 ms not, configs[3] 0.249 / 0.171; the headline shape, 40 KB
-    // staged, stays).  UPR_LS_STAGE_FULL = 0 / 1 forces either form (A/B runs).
-    static const int stage_env = getenv("UPR_LS_STAGE_FULL") ? atoi(getenv("UPR_LS_STAGE_FULL")) : -1;
-    const bool stage_off = stage_env == 0 || (stage_env < 0 && lds > 41 * 1024);
-    if (lds > 64 * 1024 || stage_off) {   // (also: long horizons of the large shapes, where three copies do not fit)
-        A.stage_full = 0;
-        lds = (size_t)upr_ls_lds_doubles(h->d, false) * sizeof(double) + sizeof(upr_problem) + 16;
-        if (lds > 160 * 1024) return fail("horizon too long for the line-search kernel's LDS");
-    }
+    A.stage_full = s.stage ? 1 : 0;
+    if (s.lds > 160 * 1024) return fail("horizon too long for the line-search kernel's LDS");
+    if (s.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)s.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds);
     // two waves per instance (wave 0: the chain walks of a trial, wave 1: its flat sums): 241 registers, four workgroups per CU by
     // LDS.  Four waves (more flat lanes, 128 registers a lane for four workgroups per CU: 135 spilled) measured 48 against 33 us.
-    const int nt = 128;
-    // (nfm, nbm, exact, obs: the template arguments of kern besides NQ, NT and STAGE, remembered for upr_batch_ls_kernel_name)
-    auto launch = [&](void (*kern)(upr_ls_args), int nfm, int nbm, bool exact, bool obs) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(h->B), dim3(nt), lds, h->stream, A);
-        h->ls_form[0] = nfm; h->ls_form[1] = nbm; h->ls_form[2] = exact; h->ls_form[3] = obs; h->ls_form[4] = A.stage_full != 0;
-    };
-    // small shapes (one body, up to four frictional contacts): per-lane vectors sized for them
-    // exactly the headline's contact structure (one body on the tray, four frictional contacts): every bound a constant
-    const bool st = A.stage_full != 0;   // (compile-time in the kernel: its staged arrays are LDS pointers, not generic ones)
-    if (h->d.nfc == 12 && h->d.nb == 1 && h->P.nf == 3 && h->P.nc == 4 && h->d.no == 0) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, true, false, true> : upr_linesearch_kernel<NQ, 128, 12, 1, true, false, false>, 12, 1, true, false);
-    // ... the same with state rows: collision / projectile rows (configs[4], the obstacle experiments: round 5), the end-effector box
-    // (a box-only problem skips the sphere walk: upr_ls_knot)
-    else if (h->d.nfc == 12 && h->d.nb == 1 && h->P.nf == 3 && h->P.nc == 4) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, true, true, true> : upr_linesearch_kernel<NQ, 128, 12, 1, true, true, false>, 12, 1, true, true);
-    else if (h->d.nfc <= 12 && h->d.nb == 1) launch(st ? upr_linesearch_kernel<NQ, 128, 12, 1, false, true, true> : upr_linesearch_kernel<NQ, 128, 12, 1, false, true, false>, 12, 1, false, true);
-    else launch(st ? upr_linesearch_kernel<NQ, 128, 3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true, true> : upr_linesearch_kernel<NQ, 128, 3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true, false>,
-                3 * UPR_MAX_CONTACTS, UPR_MAX_BODIES, false, true);
+    hipLaunchKernelGGL(s.kern, dim3(h->B), dim3(128), s.lds, h->stream, A);
+    h->ls_launched = true;
     UPR_HIP(hipGetLastError());
     return 0;
 }
@@ -736,10 +696,6 @@ upr_qp_args make_qp_args(upr_batch* h) {
     upr_qp_args A;
     A.P = h->dP; A.d = h->d; A.xs = h->xs; A.us = h->us; A.x0 = h->x0; A.lin = h->lin; A.Df = h->Df; A.ws = h->ws; A.stats = h->stats; A.prof = h->prof; A.iter_key = h->iter_key;
     return A;
-}
-
-int do_linearize(upr_batch* h, const upr_lin_args& A) {
-    return (h->P.nq == 6) ? launch_linearize<6>(h, A) : launch_linearize<9>(h, A);
 }
 
 // Per-launch device timing with HIP events recorded on the engine's stream (no host sync inside the
@@ -806,7 +762,7 @@ int advance_impl(upr_batch* h) {
     const int sqp_iters = h->sqp_iters_next > 0 ? h->sqp_iters_next : h->P.sqp_iters;
     h->sqp_iters_next = 0;
     for (int it = 0; it < sqp_iters; ++it) {
-        { KernelTimer T(h, 0); if (do_linearize(h, traj_lin_args(h))) return 1; T.stop(); }
+        { KernelTimer T(h, 0); if (launch_linearize(h, traj_lin_args(h))) return 1; T.stop(); }
         {
             upr_qp_args Q = make_qp_args(h);
             // the production kernel writes the feedback gains of the advance's LAST QP itself (no gather kernel afterwards)
@@ -833,7 +789,7 @@ int advance_impl(upr_batch* h) {
         // of its own) and, behind the advance's last line search, the copy of the solution the next warm start reads
         if (h->order_on) { L.order_out = h->order; L.iter_key = h->iter_key; }
         if (it == sqp_iters - 1) { L.xs_prev = h->xs_prev; L.us_prev = h->us_prev; L.tprev = h->tprev; }
-        { KernelTimer T(h, 2); int rc = (h->P.nq == 6) ? launch_linesearch<6>(h, L) : launch_linesearch<9>(h, L); if (rc) return 1; T.stop(); }
+        { KernelTimer T(h, 2); if (launch_linesearch(h, L)) return 1; T.stop(); }
         if (h->order_on) h->order_valid = true;
     }
     if (h->fb && !(h->qp.fb_fused && sqp_iters > 0)) {   // sqp.use_feedback_policy: gains of the last QP, before anything overwrites its factors
@@ -1028,8 +984,20 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
         qp_resolve(s, *P, d);
         h->d.ws_stride = s.ws_stride;
     }
-    if (const char* e = getenv("UPR_LIN_MFMA")) h->use_mfma = atoi(e) != 0;
-    if (const char* e = getenv("UPR_LIN2")) h->lin2 = atoi(e) != 0;
+    {   // ... and its linearisation and line-search kernels (upr_launch_select.h)
+        upr_lin_knobs kl; upr_ls_knobs ks;
+        if (const char* e = getenv("UPR_LIN_MFMA")) kl.mfma = atoi(e) != 0;
+        if (const char* e = getenv("UPR_LIN2")) kl.lin2 = atoi(e) != 0;
+        if (const char* e = getenv("UPR_LIN_OCC")) kl.occ = atoi(e);
+        if (const char* e = getenv("UPR_LIN_ROW_PASSES")) kl.row_passes = atoi(e);
+        if (const char* e = getenv("UPR_LS_STAGE_FULL")) ks.stage_full = atoi(e);
+        static_cast<upr_lin_choice&>(h->lin_sel) = upr_lin_plan(*P, d, kl);
+        static_cast<upr_ls_choice&>(h->ls_sel) = upr_ls_plan(*P, d, ks);
+        h->lin_sel.kern = (P->nq == 6) ? lin_kernel<6>(h->lin_sel) : lin_kernel<9>(h->lin_sel);
+        h->ls_sel.kern = (P->nq == 6) ? ls_kernel<6>(h->ls_sel) : ls_kernel<9>(h->ls_sel);
+        upr_ls_name(h->ls_sel, h->ls_sel.name, sizeof(h->ls_sel.name));
+        if (!h->lin_sel.kern || !h->ls_sel.kern) { fail("the planned linearisation / line-search form is not an instantiation of upr_launch_select.h's lists"); delete h; return nullptr; }
+    }
     if (const char* e = getenv("UPR_QP_ORDER")) h->order_on = atoi(e) != 0;
     if (const char* e = getenv("UPR_BAL_FORM")) h->bal_lane = atoi(e) != 0;
     auto bad = [&]() { upr_batch_destroy(h); return (upr_batch*)nullptr; };
@@ -1230,22 +1198,14 @@ double upr_batch_last_solve_ms(const upr_batch* h) { return h ? h->last_ms : 0.0
 const char* upr_batch_qp_kernel_name(const upr_batch* h) { return h ? h->qp.name : ""; }
 
 const char* upr_batch_ls_kernel_name(upr_batch* h) {
-    if (!h || h->ls_form[4] < 0) return "";
-    const int* f = h->ls_form;
-    char buf[128];
-    snprintf(buf, sizeof(buf), "upr_linesearch_kernel<%d, 128, %d, %d, %s, %s, %s>", h->P.nq, f[0], f[1], f[2] ? "true" : "false", f[3] ? "true" : "false", f[4] ? "true" : "false");
-    h->ls_name = buf;
-    return h->ls_name.c_str();
+    if (!h || !h->ls_launched) return "";   // (none before the first launch)
+    return h->ls_sel.name;
 }
 
 const char* upr_batch_lin_kernel_name(upr_batch* h) {
-    if (!h || h->lin_form[0] < 0) return "";
-    const int* f = h->lin_form;
-    char buf[128];
-    if (f[0] == 2) snprintf(buf, sizeof(buf), "upr_linearize2_kernel<%d> kpw=%d blocks=%d", h->P.nq, f[1], f[2]);
-    else snprintf(buf, sizeof(buf), "upr_linearize_kernel<%d, %s, %d, %s, %d>", h->P.nq, f[1] ? "true" : "false", f[2], f[3] ? "true" : "false", f[4]);
-    h->lin_name = buf;
-    return h->lin_name.c_str();
+    if (!h || h->lin_blocks_last < 0) return "";
+    upr_lin_name(h->lin_sel, h->lin_blocks_last, h->lin_sel.name, sizeof(h->lin_sel.name));
+    return h->lin_sel.name;
 }
 
 /* restore == 0: keep a copy of the per-instance statistics and of the QP dispatch keys of the last advance; restore != 0: put that
@@ -1295,7 +1255,7 @@ static int linearize_points_impl(upr_batch* h, int n, const int* inst, const dou
         if (dyn_pts) UPR_HIP(hipMemcpy(ddyn, dyn_pts, sizeof(double) * n * 9 * h->P.n_dyn, hipMemcpyHostToDevice));
         A.dyn = ddyn; A.pflag = h->pflag;
     }
-    if (do_linearize(h, A)) return 1;
+    if (launch_linearize(h, A)) return 1;
     UPR_HIP(hipStreamSynchronize(h->stream));
     rec.assign((size_t)n * d.lin_stride, 0.0);
     UPR_HIP(hipMemcpy(rec.data(), dlin, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
@@ -1380,7 +1340,7 @@ int upr_batch_eq_input_jacobian(upr_batch* h, int inst, double* gu) {
 // linearise at the current trajectory and solve one QP there with the multiplier export (no synchronisation)
 static int kkt_launch(upr_batch* h) {
     if (h->qp.exported && !h->kkt && dev_alloc(&h->kkt, (size_t)h->B * h->qp.stride)) return 1;
-    if (do_linearize(h, traj_lin_args(h))) return 1;
+    if (launch_linearize(h, traj_lin_args(h))) return 1;
     upr_qp_args A = make_qp_args(h);
     if (h->qp.exported) { A.kkt = h->kkt; A.kkt_stride = h->qp.stride; }
     return launch_qp(h, A);
@@ -1389,7 +1349,7 @@ static int kkt_launch(upr_batch* h) {
 static int qp_step_core(upr_batch* h, double* dxs, double* dus) {
     UPR_ENTER(h);
     const upr_dims& d = h->d;
-    if (do_linearize(h, traj_lin_args(h))) return 1;
+    if (launch_linearize(h, traj_lin_args(h))) return 1;
     if (launch_qp(h, make_qp_args(h))) return 1;
     UPR_HIP(hipStreamSynchronize(h->stream));
     std::vector<double> ws((size_t)h->B * d.ws_stride);

@@ -465,6 +465,10 @@ static UPR_HDI void upr_lin_phase2(const upr_lin_args& A, const upr_lin_point& q
     }
 }
 
+// passes per workgroup of the multi-pass instantiation (host arithmetic reads it too: upr_launch_select.h)
+#ifndef UPR_LIN_PASSES
+#define UPR_LIN_PASSES 3   // (measured, headline: 1 pass 0.085 ms, 2: 0.079, 3: 0.073, 4: 0.102 -- LDS then allows one workgroup less per CU)
+#endif
 #ifndef UPR_HOST_EMU
 #ifdef UPR_LIN_PROF
 // instrumented build (-DUPR_LIN_PROF): cycles per phase, summed over the workgroups by lane 0 (upr_debug_lin_prof reads them)
@@ -478,9 +482,6 @@ __device__ unsigned long long upr_lin_prof[8];
 // number of active lanes: the workgroup's 8 x PASSES walks run side by side on the first lanes of wave 0, ONCE, and the
 // other phases loop over the passes.
 // OCC: waves per SIMD the register allocation is held to (the kernel is latency bound: more resident knots hide more of it)
-#ifndef UPR_LIN_PASSES
-#define UPR_LIN_PASSES 3   // (measured, headline: 1 pass 0.085 ms, 2: 0.079, 3: 0.073, 4: 0.102 -- LDS then allows one workgroup less per CU)
-#endif
 // NPASS: passes per workgroup (UPR_LIN_PASSES for problems without collision rows; with them the per-knot LDS area is three
 // times larger and one pass per workgroup measured best: configs[2] 1.11 ms against 1.70 ms with three passes)
 template <int NQ, bool USE_MFMA, int OCC = 2, bool ORI = false, int NPASS = 1>
