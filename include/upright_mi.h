@@ -401,6 +401,32 @@ int upr_batch_friction_margin_points(upr_batch* h, int n, const double* x, int n
                                      double kappa_max, double* kappa_hi, double* kappa_lo, double* z, double* y, int* iters);
 int upr_batch_friction_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double kappa_max,
                                    double* kappa_hi, double* kappa_lo, int* iters);
+/* The balance check with a friction scale per scenario AND contact: mu_scale_c[n_scen][nc], finite and >= 0, mu_i -> mu_scale_c[s][i]
+ * mu_i.  upright_cmd/scripts/tools/compute_minimum_mu.py:12-30 gives every pair of objects its own friction coefficient; this is rho
+ * for such a vector.  Rows that are uniform over the contacts give the bits of the _mu calls, all ones those of the plain calls. */
+int upr_batch_balance_points_cmu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point,
+                                 const double* mu_scale_c, double* rho, double* z, int* iters);
+int upr_batch_balance_plan_cmu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale_c, double* rho,
+                               int* iters);
+/* Friction margin per contact group: which interface binds a state (compute_minimum_mu.py:12-30, compute_contact_idx: one friction
+ * coefficient per pair of objects).  group_mask[n_grp]: bit i of word g set -- contact i belongs to group g (groups may overlap;
+ * every mask non-empty, no bit >= nc).  mu_base[n_scen][nc], finite and >= 0, or NULL (ones): the scale of the contacts outside the
+ * group.  With A_g(kappa) built on kappa mu_i inside group g and mu_base[s][i] mu_i outside,
+ *       kappa*_g = inf { kappa in [0, kappa_max] : rho_g(kappa) <= 1e-8 max(|b|, 1) },   +inf if kappa_max fails
+ *   by the algorithm and with the outputs of the friction margin above, every one with a trailing group axis:
+ *   kappa_hi[n][n_scen][n_grp], kappa_lo, iters likewise, z[n][n_scen][n_grp][ncol], y[n][n_scen][n_grp][6 nb].  kappa*_g = 0: the
+ *   friction of group g is not needed; +inf: more friction on group g alone does not help.  One group of all contacts without
+ *   mu_base gives the bits of upr_batch_friction_margin_points.  The force bounds u_lb / u_ub are NOT part of it.
+ *   upr_batch_friction_margin_groups_plan  the knots of the current plan: kappa_hi[B][N+1][n_scen][n_grp] or NULL; worst[B][n_scen]
+ *       [n_grp] or NULL: the largest kappa_hi over the knots (+inf counts as largest), reduced on the device, worst_knot (or NULL)
+ *       the first knot that attains it -- with kappa_hi NULL only these are downloaded.  kappa_hi and worst must not both be NULL.
+ *   Scratch, timing and the state of the handle as the friction margin above. */
+int upr_batch_friction_margin_groups_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point,
+                                            int n_grp, const unsigned* group_mask, const double* mu_base, double kappa_max,
+                                            double* kappa_hi, double* kappa_lo, double* z, double* y, int* iters);
+int upr_batch_friction_margin_groups_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_grp,
+                                          const unsigned* group_mask, const double* mu_base, double kappa_max, double* kappa_hi,
+                                          double* kappa_lo, int* iters, double* worst, int* worst_knot);
 /* device time (ms) of the two kernel launches of the last balance check or friction margin on the handle, HIP events around them
  * (copies excluded) */
 double upr_batch_balance_ms(upr_batch* h);

@@ -828,23 +828,34 @@ int balance_check_params(const upr_batch* h, const double* params, size_t count)
         if (!(params[10 * i] > 0) || !std::isfinite(params[10 * i])) return fail("balance check: every body of every scenario needs a positive finite mass");
     return 0;
 }
-// mu_scale_host: the friction scale of every scenario ([n_scen]) or NULL: ones.  mar: NULL for the rho calls; else the friction-margin
-// call (upr_margin.h) on the same jobs -- rho is not written, z is the one at kappa_hi, iters the solves over all evaluations.
+// mu_scale_host: the friction scale of every scenario ([n_scen]; with mu_per_contact [n_scen][nc]) or NULL: ones.  mar: NULL for the
+// rho calls; else the friction-margin call (upr_margin.h) on the same jobs -- rho is not written, z is the one at kappa_hi, iters the
+// solves over all evaluations.  grp (with mar): the margin of every contact group, outputs [n][n_scen][n_grp]; base the table of base
+// scales ([n_scen][nc]) or NULL; worst / worst_knot ([n / nk][n_scen][n_grp], either may be NULL): the largest kappa_hi over the nk
+// knots of an instance, reduced on the device; mar->hi may then be NULL and kappa_hi stays on the device.
 struct bal_margin_out { double kappa_max; double* hi; double* lo; double* y; };
+struct bal_group_in { int n_grp; const unsigned* mask; const double* base; double* worst; int* worst_knot; int nk; };
 int balance_run(upr_batch* h, long long n, const double* x_host, const double* dx, int n_scen, const double* params_host, size_t params_count,
                 const double* dparams, int pdiv, double* rho, double* z, int* iters, const double* mu_scale_host = nullptr,
-                const bal_margin_out* mar = nullptr) {
+                const bal_margin_out* mar = nullptr, bool mu_per_contact = false, const bal_group_in* grp = nullptr) {
     const upr_dims& d = h->d;
     const upr_bal_dims L = upr_bal_layout(d.nb, d.nc, d.nf);
-    const long long njobs = n * n_scen;
-    if (n > (1ll << 31) - 64 || njobs > (1ll << 36)) return fail("balance check: too many points");
-    const size_t o_st = 0, o_rho = o_st + bal_up(sizeof(double) * n * UPR_BAL_ST), o_z = o_rho + bal_up(sizeof(double) * njobs),
-                 o_it = o_z + (z ? bal_up(sizeof(double) * njobs * L.ncol) : 0), o_par = o_it + (iters ? bal_up(sizeof(int) * njobs) : 0),
+    const long long njobs = n * n_scen, ng = grp ? grp->n_grp : 1, nout = njobs * ng;
+    if (n > (1ll << 31) - 64 || nout > (1ll << 36)) return fail("balance check: too many points");
+    const double* mu_host = grp ? grp->base : mu_scale_host;
+    const size_t mu_count = (size_t)n_scen * ((grp || mu_per_contact) ? d.nc : 1);
+    const bool want_worst = grp && (grp->worst || grp->worst_knot);
+    const long long nworst = want_worst ? (n / grp->nk) * n_scen * ng : 0;
+    const size_t o_st = 0, o_rho = o_st + bal_up(sizeof(double) * n * UPR_BAL_ST), o_z = o_rho + bal_up(sizeof(double) * nout),
+                 o_it = o_z + (z ? bal_up(sizeof(double) * nout * L.ncol) : 0), o_par = o_it + (iters ? bal_up(sizeof(int) * nout) : 0),
                  o_x = o_par + (params_host ? bal_up(sizeof(double) * params_count * d.nb * 10) : 0),
                  o_mu = o_x + (x_host ? bal_up(sizeof(double) * n * d.nx) : 0),
-                 o_lo = o_mu + (mu_scale_host ? bal_up(sizeof(double) * n_scen) : 0),
-                 o_y = o_lo + ((mar && mar->lo) ? bal_up(sizeof(double) * njobs) : 0),
-                 total = o_y + ((mar && mar->y) ? bal_up(sizeof(double) * njobs * L.m) : 0);
+                 o_lo = o_mu + (mu_host ? bal_up(sizeof(double) * mu_count) : 0),
+                 o_y = o_lo + ((mar && mar->lo) ? bal_up(sizeof(double) * nout) : 0),
+                 o_gm = o_y + ((mar && mar->y) ? bal_up(sizeof(double) * nout * L.m) : 0),
+                 o_w = o_gm + (grp ? bal_up(sizeof(unsigned) * ng) : 0),
+                 o_wk = o_w + bal_up(sizeof(double) * nworst),
+                 total = o_wk + bal_up(sizeof(int) * nworst);
     if (balance_scratch(h, total)) return 1;
     char* base = (char*)h->bal_buf;
     double* dst = (double*)(base + o_st); double* drho = (double*)(base + o_rho); double* dz = (double*)(base + o_z); int* dit = (int*)(base + o_it);
@@ -857,7 +868,8 @@ int balance_run(upr_batch* h, long long n, const double* x_host, const double* d
         UPR_HIP(hipMemcpyAsync(base + o_x, x_host, sizeof(double) * n * d.nx, hipMemcpyHostToDevice, h->stream));
         dx = (const double*)(base + o_x);
     }
-    if (mu_scale_host) UPR_HIP(hipMemcpyAsync(base + o_mu, mu_scale_host, sizeof(double) * n_scen, hipMemcpyHostToDevice, h->stream));
+    if (mu_host) UPR_HIP(hipMemcpyAsync(base + o_mu, mu_host, sizeof(double) * mu_count, hipMemcpyHostToDevice, h->stream));
+    if (grp) UPR_HIP(hipMemcpyAsync(base + o_gm, grp->mask, sizeof(unsigned) * ng, hipMemcpyHostToDevice, h->stream));
     if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
     UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
     const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
@@ -867,29 +879,43 @@ int balance_run(upr_batch* h, long long n, const double* x_host, const double* d
     upr_bal_args A;
     A.P = h->dP; A.n = (int)n; A.n_scen = n_scen; A.st = dst; A.params = dparams; A.pdiv = pdiv; A.eq_scale = d.eq_scale;
     A.rho = drho; A.z = z ? dz : nullptr; A.iters = iters ? dit : nullptr;
-    A.mu_scale = mu_scale_host ? (const double*)(base + o_mu) : nullptr;
+    A.mu_scale = (mu_scale_host && !grp) ? (const double*)(base + o_mu) : nullptr;
     upr_mar_args M;
     if (mar) { M.J = A; M.J.rho = nullptr; M.kappa_max = mar->kappa_max; M.kappa_hi = drho; M.kappa_lo = mar->lo ? dlo : nullptr; M.y = mar->y ? dy : nullptr; }
+    upr_grp_args X;
+    if (grp) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = grp->base ? (const double*)(base + o_mu) : nullptr; }
     // the wave-per-job kernels: jobs are dealt round robin to a grid that fills the device a few times over (a workgroup is one
     // wave; its LDS, at most 26.4 KB, lets six of the largest shape share a CU inside the 160 KiB)
     const dim3 lane_grid((unsigned)((njobs + 63) / 64)), wave_grid((unsigned)(njobs < 16384 ? njobs : 16384));
     const size_t lds = (size_t)L.total * sizeof(double);
     if (upr_bal_lane_form(d.nb) && h->bal_lane) {
-        if (mar) hipLaunchKernelGGL(upr_bal_margin1_kernel, lane_grid, dim3(64), 0, h->stream, M, L, njobs);
+        if (grp) hipLaunchKernelGGL(upr_bal_margin1_grp_kernel, dim3(lane_grid.x, (unsigned)ng), dim3(64), 0, h->stream, X, L, njobs);
+        else if (mar) hipLaunchKernelGGL(upr_bal_margin1_kernel, lane_grid, dim3(64), 0, h->stream, M, L, njobs);
+        else if (A.mu_scale && mu_per_contact) hipLaunchKernelGGL(upr_bal_project1_cmu_kernel, lane_grid, dim3(64), 0, h->stream, A, L, njobs);
         else if (A.mu_scale) hipLaunchKernelGGL(upr_bal_project1_mu_kernel, lane_grid, dim3(64), 0, h->stream, A, L, njobs);
         else hipLaunchKernelGGL(upr_bal_project1_kernel, lane_grid, dim3(64), 0, h->stream, A, L, njobs);
     } else {
-        if (mar) hipLaunchKernelGGL(upr_bal_margin_kernel, wave_grid, dim3(64), lds, h->stream, M, L, njobs);
+        if (grp) hipLaunchKernelGGL(upr_bal_margin_grp_kernel, dim3((unsigned)(nout < 16384 ? nout : 16384)), dim3(64), lds, h->stream, X, L, nout);
+        else if (mar) hipLaunchKernelGGL(upr_bal_margin_kernel, wave_grid, dim3(64), lds, h->stream, M, L, njobs);
+        else if (A.mu_scale && mu_per_contact) hipLaunchKernelGGL(upr_bal_project_cmu_kernel, wave_grid, dim3(64), lds, h->stream, A, L, njobs);
         else if (A.mu_scale) hipLaunchKernelGGL(upr_bal_project_mu_kernel, wave_grid, dim3(64), lds, h->stream, A, L, njobs);
         else hipLaunchKernelGGL(upr_bal_project_kernel, wave_grid, dim3(64), lds, h->stream, A, L, njobs);
     }
     UPR_HIP(hipGetLastError());
+    if (want_worst) {
+        hipLaunchKernelGGL(upr_bal_margin_worst_kernel, dim3((unsigned)((nworst + 63) / 64)), dim3(64), 0, h->stream, (const double*)drho, grp->nk,
+                           (long long)n_scen * ng, nworst, (double*)(base + o_w), grp->worst_knot ? (int*)(base + o_wk) : nullptr);
+        UPR_HIP(hipGetLastError());
+    }
     UPR_HIP(hipEventRecord(h->bal_ev[1], h->stream));
-    UPR_HIP(hipMemcpyAsync(mar ? mar->hi : rho, drho, sizeof(double) * njobs, hipMemcpyDeviceToHost, h->stream));
-    if (z) UPR_HIP(hipMemcpyAsync(z, dz, sizeof(double) * njobs * L.ncol, hipMemcpyDeviceToHost, h->stream));
-    if (iters) UPR_HIP(hipMemcpyAsync(iters, dit, sizeof(int) * njobs, hipMemcpyDeviceToHost, h->stream));
-    if (mar && mar->lo) UPR_HIP(hipMemcpyAsync(mar->lo, dlo, sizeof(double) * njobs, hipMemcpyDeviceToHost, h->stream));
-    if (mar && mar->y) UPR_HIP(hipMemcpyAsync(mar->y, dy, sizeof(double) * njobs * L.m, hipMemcpyDeviceToHost, h->stream));
+    double* hi_host = mar ? mar->hi : rho;
+    if (hi_host) UPR_HIP(hipMemcpyAsync(hi_host, drho, sizeof(double) * nout, hipMemcpyDeviceToHost, h->stream));
+    if (z) UPR_HIP(hipMemcpyAsync(z, dz, sizeof(double) * nout * L.ncol, hipMemcpyDeviceToHost, h->stream));
+    if (iters) UPR_HIP(hipMemcpyAsync(iters, dit, sizeof(int) * nout, hipMemcpyDeviceToHost, h->stream));
+    if (mar && mar->lo) UPR_HIP(hipMemcpyAsync(mar->lo, dlo, sizeof(double) * nout, hipMemcpyDeviceToHost, h->stream));
+    if (mar && mar->y) UPR_HIP(hipMemcpyAsync(mar->y, dy, sizeof(double) * nout * L.m, hipMemcpyDeviceToHost, h->stream));
+    if (want_worst && grp->worst) UPR_HIP(hipMemcpyAsync(grp->worst, base + o_w, sizeof(double) * nworst, hipMemcpyDeviceToHost, h->stream));
+    if (want_worst && grp->worst_knot) UPR_HIP(hipMemcpyAsync(grp->worst_knot, base + o_wk, sizeof(int) * nworst, hipMemcpyDeviceToHost, h->stream));
     UPR_HIP(hipStreamSynchronize(h->stream));
     float ms = 0.0f;
     UPR_HIP(hipEventElapsedTime(&ms, h->bal_ev[0], h->bal_ev[1]));
@@ -899,6 +925,23 @@ int balance_run(upr_batch* h, long long n, const double* x_host, const double* d
 int balance_check_mu(const double* mu_scale, int n_scen) {
     if (mu_scale) for (int s = 0; s < n_scen; ++s)
         if (!(mu_scale[s] >= 0) || !std::isfinite(mu_scale[s])) return fail("balance check: every mu_scale must be finite and >= 0");
+    return 0;
+}
+// a scale per scenario and contact (mu_scale_c of the _cmu calls, mu_base of the group margin)
+int balance_check_cmu(const double* v, size_t count, const char* what) {
+    if (v) for (size_t i = 0; i < count; ++i)
+        if (!(v[i] >= 0) || !std::isfinite(v[i])) return fail(std::string("balance check: every ") + what + " must be finite and >= 0");
+    return 0;
+}
+int balance_check_groups(const upr_batch* h, int n_grp, const unsigned* group_mask) {
+    if (n_grp < 1 || n_grp > 65535) return fail("friction margin of contact groups: n_grp must be in 1 .. 65535");
+    if (!group_mask) return fail("friction margin of contact groups: group_mask must not be NULL");
+    const int nc = h->d.nc;
+    for (int g = 0; g < n_grp; ++g) {
+        if (group_mask[g] == 0u) return fail("friction margin of contact groups: group " + std::to_string(g) + " has an empty mask");
+        if (nc < 32 && (group_mask[g] >> nc) != 0u)
+            return fail("friction margin of contact groups: group " + std::to_string(g) + " has a mask bit >= nc = " + std::to_string(nc));
+    }
     return 0;
 }
 int balance_check_kappa(double kappa_max) {
@@ -1604,17 +1647,20 @@ int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, c
 
 // the plan's knots: the jobs of both plan calls (rho, or with mar the friction margin)
 static int balance_plan_run(upr_batch* h, const char* who, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho,
-                            double* z, int* iters, const bal_margin_out* mar) {
+                            double* z, int* iters, const bal_margin_out* mar, bool mu_per_contact = false, const bal_group_in* grp = nullptr) {
     const long long n = (long long)h->B * (h->d.N + 1);
+    const int nmu = mu_per_contact ? h->d.nc : 1;
     if (!params) {   // the nominal check: every instance against its own body parameters
         if (n_scen != 1) return fail(std::string(who) + ": params == NULL needs n_scen == 1 (every instance's own body parameters)");
-        if (balance_check_mu(mu_scale, 1)) return 1;
-        return balance_run(h, n, nullptr, h->xs, 1, nullptr, 0, h->body_params, h->d.N + 1, rho, z, iters, mu_scale, mar);
+        if (balance_check_mu(mu_scale, nmu) || (grp && balance_check_cmu(grp->base, h->d.nc, "mu_base"))) return 1;
+        return balance_run(h, n, nullptr, h->xs, 1, nullptr, 0, h->body_params, h->d.N + 1, rho, z, iters, mu_scale, mar, mu_per_contact, grp);
     }
     if (n_scen < 1) return fail(std::string(who) + ": n_scen must be >= 1");
     const size_t count = (size_t)(per_instance ? h->B : 1) * n_scen;
-    if (balance_check_params(h, params, count) || balance_check_mu(mu_scale, n_scen)) return 1;
-    return balance_run(h, n, nullptr, h->xs, n_scen, params, count, nullptr, per_instance ? h->d.N + 1 : 0, rho, z, iters, mu_scale, mar);
+    if (balance_check_params(h, params, count) || balance_check_mu(mu_scale, n_scen * nmu)) return 1;
+    if (grp && balance_check_cmu(grp->base, (size_t)n_scen * h->d.nc, "mu_base")) return 1;
+    return balance_run(h, n, nullptr, h->xs, n_scen, params, count, nullptr, per_instance ? h->d.N + 1 : 0, rho, z, iters, mu_scale, mar, mu_per_contact,
+                       grp);
 }
 
 int upr_batch_balance_plan_mu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho, int* iters) {
@@ -1646,6 +1692,49 @@ int upr_batch_friction_margin_plan(upr_batch* h, int n_scen, const double* param
     if (!kappa_hi) return fail("upr_batch_friction_margin_plan: kappa_hi must not be NULL");
     const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, nullptr};
     return balance_plan_run(h, "upr_batch_friction_margin_plan", n_scen, params, per_instance, nullptr, nullptr, nullptr, iters, &mar);
+}
+
+int upr_batch_balance_points_cmu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, const double* mu_scale_c,
+                                 double* rho, double* z, int* iters) {
+    UPR_ENTER(h);
+    if (n <= 0) return 0;
+    if (!x || !params || !rho || !mu_scale_c) return fail("upr_batch_balance_points_cmu: x, params, mu_scale_c and rho must not be NULL");
+    if (n_scen < 1) return fail("upr_batch_balance_points_cmu: n_scen must be >= 1");
+    const size_t count = (size_t)(per_point ? n : 1) * n_scen;
+    if (balance_check_params(h, params, count) || balance_check_mu(mu_scale_c, n_scen * h->d.nc)) return 1;
+    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, rho, z, iters, mu_scale_c, nullptr, true);
+}
+
+int upr_batch_balance_plan_cmu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale_c, double* rho, int* iters) {
+    UPR_ENTER(h);
+    if (!rho || !mu_scale_c) return fail("upr_batch_balance_plan_cmu: mu_scale_c and rho must not be NULL");
+    return balance_plan_run(h, "upr_batch_balance_plan_cmu", n_scen, params, per_instance, mu_scale_c, rho, nullptr, iters, nullptr, true);
+}
+
+int upr_batch_friction_margin_groups_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, int n_grp,
+                                            const unsigned* group_mask, const double* mu_base, double kappa_max, double* kappa_hi, double* kappa_lo,
+                                            double* z, double* y, int* iters) {
+    UPR_ENTER(h);
+    if (balance_check_kappa(kappa_max) || balance_check_groups(h, n_grp, group_mask)) return 1;
+    if (n <= 0) return 0;
+    if (!x || !params || !kappa_hi) return fail("upr_batch_friction_margin_groups_points: x, params and kappa_hi must not be NULL");
+    if (n_scen < 1) return fail("upr_batch_friction_margin_groups_points: n_scen must be >= 1");
+    const size_t count = (size_t)(per_point ? n : 1) * n_scen;
+    if (balance_check_params(h, params, count) || balance_check_cmu(mu_base, (size_t)n_scen * h->d.nc, "mu_base")) return 1;
+    const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, y};
+    const bal_group_in grp = {n_grp, group_mask, mu_base, nullptr, nullptr, 1};
+    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, nullptr, z, iters, nullptr, &mar, false, &grp);
+}
+
+int upr_batch_friction_margin_groups_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_grp, const unsigned* group_mask,
+                                          const double* mu_base, double kappa_max, double* kappa_hi, double* kappa_lo, int* iters, double* worst,
+                                          int* worst_knot) {
+    UPR_ENTER(h);
+    if (balance_check_kappa(kappa_max) || balance_check_groups(h, n_grp, group_mask)) return 1;
+    if (!kappa_hi && !worst) return fail("upr_batch_friction_margin_groups_plan: kappa_hi and worst must not both be NULL");
+    const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, nullptr};
+    const bal_group_in grp = {n_grp, group_mask, mu_base, worst, worst_knot, h->d.N + 1};
+    return balance_plan_run(h, "upr_batch_friction_margin_groups_plan", n_scen, params, per_instance, nullptr, nullptr, nullptr, iters, &mar, false, &grp);
 }
 
 double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }

@@ -88,7 +88,8 @@ struct upr_bal_args {
     double* z;               // [n][n_scen][ncol] or NULL
     int* iters;              // [n][n_scen] or NULL
     // friction scale of every scenario, [n_scen] -- the generators of contact i are formed with mu_scale[sc] mu_i (the --mu of
-    // process_sim_runs.py as a scenario axis); read by the _mu kernels only
+    // process_sim_runs.py as a scenario axis); read by the _mu kernels only.  The _cmu kernels read it as [n_scen][nc]: a scale per
+    // scenario and contact (every pair of objects its own friction coefficient, compute_minimum_mu.py:12-30)
     const double* mu_scale = nullptr;
 };
 
@@ -102,15 +103,27 @@ static UPR_HDI void upr_bal_state_point(const upr_problem* P, const double* x, d
 }
 
 // ---- column j of A: the blocks on contact_body1 (ba = -1: the end effector, no block) and contact_body2 ----------------------------
-// kap: the friction scale, the pyramid of contact i is built on kap mu_i (kap = 1: mu_i * 1.0 is exact, the column is bit for bit
-// the one without a scale; nf = 1 generators carry no mu)
+// mu: the source of the friction scale, the pyramid of contact i is built on mu.at(i) mu_i (a scale of 1: mu_i * 1.0 is exact, the
+// column is bit for bit the one without a scale; nf = 1 generators carry no mu).  Three sources:
+//   upr_bal_mu_one  the constant 1 (the calls without a friction scale: folds away);
+//   upr_bal_mu_all  one scale for every contact (a scenario's mu_scale; the kappa of the common friction margin);
+//   upr_bal_mu_grp  per contact: kap on the contacts of a group (a 32-bit mask, UPR_MAX_CONTACTS = 32), elsewhere the base scale
+//                   base[i] of the job's scenario, read from global memory next to contact_mu[i], or 1 without a table.  An empty
+//                   mask with a table is the plain per-contact scale of the _cmu kernels.
+struct upr_bal_mu_one { UPR_HDI double at(int) const { return 1.0; } };
+struct upr_bal_mu_all { double kap; UPR_HDI double at(int) const { return kap; } };
+struct upr_bal_mu_grp {
+    unsigned mask; double kap; const double* base;
+    UPR_HDI double at(int i) const { return ((mask >> i) & 1u) ? kap : (base ? base[i] : 1.0); }
+};
+template <class MU = upr_bal_mu_one>
 static UPR_HDI void upr_bal_column(const upr_problem* P, const double* bp, double scale, int gpc, int j, int* ba, double* va, int* bb, double* vb,
-                                   double kap = 1.0) {
+                                   const MU& mu = MU()) {
     const int i = j / gpc, g = j - i * gpc;
     double d[3];
     for (int a = 0; a < 3; ++a) d[a] = P->contact_normal[i][a];
     if (gpc == 4) {
-        const double sm = ((g < 2) ? 1.0 : -1.0) * (P->contact_mu[i] * kap);
+        const double sm = ((g < 2) ? 1.0 : -1.0) * (P->contact_mu[i] * mu.at(i));
         const double* s = P->contact_span[i] + 3 * (g & 1);
         for (int a = 0; a < 3; ++a) d[a] += sm * s[a];
     }
@@ -230,12 +243,13 @@ static UPR_HDI void upr_bal_solve(const upr_ctx& ctx, int mp, int np, const doub
 }
 
 // ---- the projection of one job: the lanes of ctx work on it together, W: L.total doubles of workspace (LDS) -------------------------
-// b (W + L.o_b) is written by the caller, not yet synchronised; kap: the friction scale of the generators.  A cold start: nothing of
-// an earlier projection in W is read.  Leaves r = b + A z (W + L.o_r), the passive slots (zp, pidx, their columns; *np_out of them),
+// b (W + L.o_b) is written by the caller, not yet synchronised; mu: the friction scale of the generators (upr_bal_column).  A cold
+// start: nothing of an earlier projection in W is read.  Leaves r = b + A z (W + L.o_r), the passive slots (zp, pidx, their columns; *np_out of them),
 // the column states and in G the Cholesky factor of the last passive system (its leading block is the factor of the slots that
 // are left unless the cap was reached); returns rho on every lane, *bnorm_out = |b|, *iters_out the least-squares solves (the cap if it was reached).
+template <class MU>
 static UPR_HDI double upr_bal_project(const upr_ctx& ctx, const upr_problem* P, const upr_bal_dims& L, const double* bp, double eq_scale,
-                                      double kap, double* W, int* np_out, int* iters_out, double* bnorm_out) {
+                                      const MU& mu, double* W, int* np_out, int* iters_out, double* bnorm_out) {
     const int m = L.m, ncol = L.ncol, mp = L.mp;
     double *b = W + L.o_b, *r = W + L.o_r, *zp = W + L.o_zp, *s = W + L.o_s, *y = W + L.o_y, *dg = W + L.o_dg, *pc = W + L.o_pcol, *G = W + L.o_G;
     int* pidx = (int*)(W + L.o_int); int* pb = pidx + mp; int* flag = pb + 2 * mp;
@@ -259,7 +273,7 @@ static UPR_HDI double upr_bal_project(const upr_ctx& ctx, const upr_problem* P, 
             UPR_FOR(j, ncol) {
                 if (flag[j] != 0) continue;
                 int ba, bq; double va[6], vb[6];
-                upr_bal_column(P, bp, eq_scale, L.gpc, j, &ba, va, &bq, vb, kap);
+                upr_bal_column(P, bp, eq_scale, L.gpc, j, &ba, va, &bq, vb, mu);
                 double w = 0.0, n2 = 0.0;
                 for (int c = 0; c < 6; ++c) { w -= vb[c] * r[6 * bq + c]; n2 += vb[c] * vb[c]; }
                 if (ba >= 0) for (int c = 0; c < 6; ++c) { w -= va[c] * r[6 * ba + c]; n2 += va[c] * va[c]; if (ba == bq) n2 += 2.0 * va[c] * vb[c]; }
@@ -277,7 +291,7 @@ static UPR_HDI double upr_bal_project(const upr_ctx& ctx, const upr_problem* P, 
         UPR_WSYNC();
         if (ctx.tid == 0) {
             int ba, bq; double va[6], vb[6];
-            upr_bal_column(P, bp, eq_scale, L.gpc, bj, &ba, va, &bq, vb, kap);
+            upr_bal_column(P, bp, eq_scale, L.gpc, bj, &ba, va, &bq, vb, mu);
             for (int c = 0; c < 6; ++c) { pc[12 * np + c] = va[c]; pc[12 * np + 6 + c] = vb[c]; }
             pb[2 * np] = ba; pb[2 * np + 1] = bq; pidx[np] = bj; zp[np] = 0.0; flag[bj] = 1;
         }
@@ -392,19 +406,27 @@ static UPR_HDI void upr_bal_put_z(const upr_ctx& ctx, const upr_bal_dims& L, con
 }
 
 // ---- one (point, scenario) job ------------------------------------------------------------------------------------------------------
-// MU: the friction scale of the job's scenario is read from A.mu_scale; without it the scale is the constant 1 and folds away (the
-// kernels of the calls without a friction scale keep the code they had before there was one)
-template <bool MU = false>
+// MU: 0 the scale is the constant 1 and folds away (the kernels of the calls without a friction scale keep the code they had before
+// there was one); 1 the friction scale of the job's scenario is read from A.mu_scale[sc]; 2 the scale of contact i is read from
+// A.mu_scale[sc nc + i]
+template <int MU> struct upr_bal_src;
+template <> struct upr_bal_src<0> { typedef upr_bal_mu_one T; static UPR_HDI T of(const upr_bal_args&, int, int) { return T(); } };
+template <> struct upr_bal_src<1> { typedef upr_bal_mu_all T; static UPR_HDI T of(const upr_bal_args& A, int sc, int) { return T{A.mu_scale[sc]}; } };
+template <> struct upr_bal_src<2> {
+    typedef upr_bal_mu_grp T;
+    static UPR_HDI T of(const upr_bal_args& A, int sc, int nc) { return T{0u, 0.0, A.mu_scale + (size_t)sc * nc}; }
+};
+template <int MU = 0>
 static UPR_HDI void upr_bal_job(const upr_ctx& ctx, const upr_bal_args& A, const upr_bal_dims& L, long long job, double* W) {
     const upr_problem* P = A.P;
     const long long pt = job / A.n_scen;
     const int sc = (int)(job - pt * A.n_scen);
     const double* bp = A.params + (size_t)10 * P->nb * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
-    const double kap = MU ? A.mu_scale[sc] : 1.0;
+    const typename upr_bal_src<MU>::T mu = upr_bal_src<MU>::of(A, sc, P->nc);
     UPR_WSYNC();   // (the previous job of this wave is done with the workspace)
     upr_bal_rhs(ctx, P, A.st + (size_t)pt * UPR_BAL_ST, bp, A.eq_scale, W + L.o_b);
     int np, iters; double bnorm;
-    const double rho = upr_bal_project(ctx, P, L, bp, A.eq_scale, kap, W, &np, &iters, &bnorm);
+    const double rho = upr_bal_project(ctx, P, L, bp, A.eq_scale, mu, W, &np, &iters, &bnorm);
     if (ctx.tid == 0) {
         A.rho[job] = rho;
         if (A.iters) A.iters[job] = iters;
@@ -419,16 +441,18 @@ static UPR_HDI void upr_bal_job(const upr_ctx& ctx, const upr_bal_args& A, const
 // in scratch; the sets of passive and barred columns are bit masks (up to 128 columns: 32 contacts).
 #define UPR_BAL1_MP 6
 static UPR_HDI bool upr_bal_bit(unsigned long long lo, unsigned long long hi, int j) { return (((j < 64) ? lo : hi) >> (j & 63)) & 1ull; }
-static UPR_HDI void upr_bal_column1(const upr_problem* P, const double* bp, double scale, int gpc, int j, double* v, double kap = 1.0) {
+template <class MU>
+static UPR_HDI void upr_bal_column1(const upr_problem* P, const double* bp, double scale, int gpc, int j, double* v, const MU& mu) {
     int ba, bb; double va[6], vb[6];
-    upr_bal_column(P, bp, scale, gpc, j, &ba, va, &bb, vb, kap);
+    upr_bal_column(P, bp, scale, gpc, j, &ba, va, &bb, vb, mu);
     for (int c = 0; c < 6; ++c) v[c] = (ba >= 0) ? va[c] + vb[c] : vb[c];
 }
-// The projection of one job on one lane, cold: b the right-hand side, thr = UPR_BAL_TOL max(|b|, 1), kap the friction scale of the
+// The projection of one job on one lane, cold: b the right-hand side, thr = UPR_BAL_TOL max(|b|, 1), mu the friction scale of the
 // generators.  Leaves r = b + A z, the passive slots (pidx, zp, their columns pc; np of them) and in G the Cholesky factor of the
 // last passive system (its leading np x np block is the factor of the np slots unless the cap was reached); returns the
 // least-squares solves (the cap if reached).
-static UPR_HDI int upr_bal_project1(const upr_problem* P, const upr_bal_dims& L, const double* bp, double eq_scale, double kap, const double (&b)[6],
+template <class MU>
+static UPR_HDI int upr_bal_project1(const upr_problem* P, const upr_bal_dims& L, const double* bp, double eq_scale, const MU& mu, const double (&b)[6],
                                     double thr, double (&r)[6], double (&zp)[UPR_BAL1_MP], int (&pidx)[UPR_BAL1_MP], int& np,
                                     double (&pc)[UPR_BAL1_MP][6], double (&G)[UPR_BAL1_MP][UPR_BAL1_MP]) {
     constexpr int MP = UPR_BAL1_MP;
@@ -454,7 +478,7 @@ static UPR_HDI int upr_bal_project1(const upr_problem* P, const upr_bal_dims& L,
             for (int j = 0; j < ncol; ++j) {
                 if (upr_bal_bit(pas0 | bar0, pas1 | bar1, j)) continue;
                 double v[6];
-                upr_bal_column1(P, bp, eq_scale, L.gpc, j, v, kap);
+                upr_bal_column1(P, bp, eq_scale, L.gpc, j, v, mu);
                 double w = 0.0, n2 = 0.0;
                 for (int c = 0; c < 6; ++c) { w -= v[c] * r[c]; n2 += v[c] * v[c]; }
                 const double nrm = sqrt(n2);
@@ -470,7 +494,7 @@ static UPR_HDI int upr_bal_project1(const upr_problem* P, const upr_bal_dims& L,
         if (iters >= cap) { capped = true; break; }
         {
             double v[6];
-            upr_bal_column1(P, bp, eq_scale, L.gpc, bj, v, kap);
+            upr_bal_column1(P, bp, eq_scale, L.gpc, bj, v, mu);
 #pragma unroll
             for (int t = 0; t < MP; ++t) if (t == np) { for (int c = 0; c < 6; ++c) pc[t][c] = v[c]; pidx[t] = bj; zp[t] = 0.0; }
             if (bj < 64) pas0 |= 1ull << bj; else pas1 |= 1ull << (bj - 64);
@@ -615,20 +639,20 @@ static UPR_HDI void upr_bal_put_z1(int ncol, const double (&zp)[UPR_BAL1_MP], co
 #pragma unroll
     for (int t = 0; t < UPR_BAL1_MP; ++t) if (t < np) zo[pidx[t]] = zp[t];
 }
-template <bool MU = false>
+template <int MU = 0>
 static UPR_HDI void upr_bal_job1(const upr_bal_args& A, const upr_bal_dims& L, long long job) {
     const upr_problem* P = A.P;
     const long long pt = job / A.n_scen;
     const int sc = (int)(job - pt * A.n_scen);
     const double* bp = A.params + (size_t)10 * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
-    const double kap = MU ? A.mu_scale[sc] : 1.0;
+    const typename upr_bal_src<MU>::T mu = upr_bal_src<MU>::of(A, sc, P->nc);
     double b[6], r[6], zp[UPR_BAL1_MP], pc[UPR_BAL1_MP][6], G[UPR_BAL1_MP][UPR_BAL1_MP];
     int pidx[UPR_BAL1_MP], np;
     upr_bal_rhs1(P, A.st + (size_t)pt * UPR_BAL_ST, bp, A.eq_scale, b);
     double bb2 = 0.0;
     for (int c = 0; c < 6; ++c) bb2 += b[c] * b[c];
     const double bnorm = sqrt(bb2), thr = UPR_BAL_TOL * (bnorm > 1.0 ? bnorm : 1.0);
-    const int iters = upr_bal_project1(P, L, bp, A.eq_scale, kap, b, thr, r, zp, pidx, np, pc, G);
+    const int iters = upr_bal_project1(P, L, bp, A.eq_scale, mu, b, thr, r, zp, pidx, np, pc, G);
     double rr = 0.0;
     for (int c = 0; c < 6; ++c) rr += r[c] * r[c];
     A.rho[job] = sqrt(rr);
@@ -661,10 +685,20 @@ __global__ __launch_bounds__(64) void upr_bal_project1_kernel(upr_bal_args A, up
 __global__ __launch_bounds__(64) void upr_bal_project_mu_kernel(upr_bal_args A, upr_bal_dims L, long long njobs) {
     extern __shared__ double upr_bal_lds[];
     upr_ctx ctx; ctx.tid = threadIdx.x; ctx.nt = 64;
-    for (long long job = blockIdx.x; job < njobs; job += gridDim.x) upr_bal_job<true>(ctx, A, L, job, upr_bal_lds);
+    for (long long job = blockIdx.x; job < njobs; job += gridDim.x) upr_bal_job<1>(ctx, A, L, job, upr_bal_lds);
 }
 __global__ __launch_bounds__(64) void upr_bal_project1_mu_kernel(upr_bal_args A, upr_bal_dims L, long long njobs) {
     const long long job = (long long)blockIdx.x * 64 + threadIdx.x;
-    if (job < njobs) upr_bal_job1<true>(A, L, job);
+    if (job < njobs) upr_bal_job1<1>(A, L, job);
+}
+// the two with a friction scale per scenario and contact (A.mu_scale as [n_scen][nc])
+__global__ __launch_bounds__(64) void upr_bal_project_cmu_kernel(upr_bal_args A, upr_bal_dims L, long long njobs) {
+    extern __shared__ double upr_bal_lds[];
+    upr_ctx ctx; ctx.tid = threadIdx.x; ctx.nt = 64;
+    for (long long job = blockIdx.x; job < njobs; job += gridDim.x) upr_bal_job<2>(ctx, A, L, job, upr_bal_lds);
+}
+__global__ __launch_bounds__(64) void upr_bal_project1_cmu_kernel(upr_bal_args A, upr_bal_dims L, long long njobs) {
+    const long long job = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (job < njobs) upr_bal_job1<2>(A, L, job);
 }
 #endif

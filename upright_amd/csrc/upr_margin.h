@@ -22,6 +22,17 @@
 // one go to global memory at the evaluation that produced them (plain stores; nothing of them is carried across projections):
 // z >= 0 with |b + A(kappa_hi) z| inside the ball proves kappa_hi feasible, and y' a_j >= 0 for every column with
 // y' b / |y| outside the ball proves kappa_lo infeasible (y' (b + A z) >= y' b for every z >= 0).
+//
+// The margin of a contact group (upr_grp_args; compute_minimum_mu.py:12-30 gives every pair of objects its own friction coefficient,
+// compute_contact_idx).  beta[sc][i] >= 0 is a base scale per scenario and contact (1 without a table), G_g a set of contacts, A_g(kappa)
+// the generator matrix built on kappa mu_i for i in G_g and on beta[sc][i] mu_i elsewhere, rho_g the distance with A_g, and
+//
+//     kappa*_g(x; theta) = inf { kappa in [0, kappa_max] : rho_g(x; theta, kappa) <= UPR_BAL_FEAS max(|b|, 1) },     +inf if there is none.
+//
+// Only the pyramids of G_g grow with kappa, so rho_g does not increase and the algorithm above holds unchanged; the group jobs are the
+// job templates below with the per-contact scale source of upr_balance.h (upr_bal_mu_grp), output index
+// (point n_scen + scenario) n_grp + group.  kappa*_g = 0: the group's friction is not needed; +inf: no friction on this group alone
+// helps.  upr_bal_margin_worst_kernel reduces kappa_hi over the knots of a plan.
 #pragma once
 #include "upr_balance.h"
 
@@ -37,6 +48,23 @@ struct upr_mar_args {
     double* kappa_hi;        // [n][n_scen]
     double* kappa_lo;        // [n][n_scen] or NULL
     double* y;               // [n][n_scen][6 nb] or NULL
+};
+
+// the group margin: the jobs of M times n_grp groups; kappa_hi, kappa_lo, iters [n][n_scen][n_grp], z [..][ncol], y [..][6 nb]
+struct upr_grp_args {
+    upr_mar_args M;
+    int n_grp;
+    const unsigned* group_mask;   // [n_grp]: bit i set -- contact i belongs to the group
+    const double* mu_base;        // [n_scen][nc] or NULL: ones
+};
+// the scale source of an evaluation at kappa: every contact (the common margin) or the contacts of the job's group
+template <bool GRP> struct upr_mar_src {
+    typedef upr_bal_mu_all T;
+    static UPR_HDI T of(unsigned, const double*, double kap) { return T{kap}; }
+};
+template <> struct upr_mar_src<true> {
+    typedef upr_bal_mu_grp T;
+    static UPR_HDI T of(unsigned mask, const double* base, double kap) { return T{mask, kap, base}; }
 };
 
 // ---- the residual of an infeasible evaluation as a certificate -----------------------------------------------------------------------
@@ -80,21 +108,28 @@ static UPR_HDI void upr_bal_polish1(const double (&pc)[UPR_BAL1_MP][6], const do
 }
 
 // ---- a wave per job ------------------------------------------------------------------------------------------------------------------
-static UPR_HDI void upr_bal_margin_job(const upr_ctx& ctx, const upr_mar_args& M, const upr_bal_dims& L, long long job, double* W) {
+// GRP: the margin of one contact group -- mask its contacts, mu_base the table of base scales (or NULL), out the index of the
+// job's outputs; without GRP the three are not read and the outputs go to index job
+template <bool GRP = false>
+static UPR_HDI void upr_bal_margin_job(const upr_ctx& ctx, const upr_mar_args& M, const upr_bal_dims& L, long long job, double* W, long long out_grp = 0,
+                                       unsigned mask = 0u, const double* mu_base = nullptr) {
+    typedef upr_mar_src<GRP> SRC;
     const upr_bal_args& A = M.J;
     const upr_problem* P = A.P;
     const long long pt = job / A.n_scen;
     const int sc = (int)(job - pt * A.n_scen);
     const double* bp = A.params + (size_t)10 * P->nb * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
-    double* zo = A.z ? A.z + (size_t)job * L.ncol : nullptr;
-    double* yo = M.y ? M.y + (size_t)job * L.m : nullptr;
+    const long long out = GRP ? out_grp : job;
+    const double* base = (GRP && mu_base) ? mu_base + (size_t)sc * P->nc : nullptr;
+    double* zo = A.z ? A.z + (size_t)out * L.ncol : nullptr;
+    double* yo = M.y ? M.y + (size_t)out * L.m : nullptr;
     const double* r = W + L.o_r;
     const int cap = upr_bal_iter_cap(L.ncol);
     UPR_WSYNC();   // (the previous job of this wave is done with the workspace)
     upr_bal_rhs(ctx, P, A.st + (size_t)pt * UPR_BAL_ST, bp, A.eq_scale, W + L.o_b);
     int np, it, total; double bnorm;
     double lo = 0.0, hi = 0.0;
-    const double rho0 = upr_bal_project(ctx, P, L, bp, A.eq_scale, 0.0, W, &np, &it, &bnorm);
+    const double rho0 = upr_bal_project(ctx, P, L, bp, A.eq_scale, SRC::of(mask, base, 0.0), W, &np, &it, &bnorm);
     total = it;
     const double lim = UPR_BAL_FEAS * (bnorm > 1.0 ? bnorm : 1.0);
     if (rho0 <= lim) {
@@ -105,7 +140,7 @@ static UPR_HDI void upr_bal_margin_job(const upr_ctx& ctx, const upr_mar_args& M
         bool feasible = false;
         if (L.gpc == 4) {
             UPR_WSYNC();
-            const double rho1 = upr_bal_project(ctx, P, L, bp, A.eq_scale, M.kappa_max, W, &np, &it, &bnorm);
+            const double rho1 = upr_bal_project(ctx, P, L, bp, A.eq_scale, SRC::of(mask, base, M.kappa_max), W, &np, &it, &bnorm);
             total += it;
             feasible = rho1 <= lim;
         }
@@ -119,7 +154,7 @@ static UPR_HDI void upr_bal_margin_job(const upr_ctx& ctx, const upr_mar_args& M
             for (int k = 0; k < UPR_BAL_BISECT; ++k) {
                 const double mid = 0.5 * (lo + hi);
                 UPR_WSYNC();
-                const double rho = upr_bal_project(ctx, P, L, bp, A.eq_scale, mid, W, &np, &it, &bnorm);
+                const double rho = upr_bal_project(ctx, P, L, bp, A.eq_scale, SRC::of(mask, base, mid), W, &np, &it, &bnorm);
                 total += it;
                 if (rho <= lim) { hi = mid; if (zo) upr_bal_put_z(ctx, L, W, np, zo); }
                 else { lo = mid; if (yo) { if (it < cap) upr_bal_polish(ctx, L, W, np); UPR_FOR(e, L.m) yo[e] = r[e]; } }
@@ -127,21 +162,26 @@ static UPR_HDI void upr_bal_margin_job(const upr_ctx& ctx, const upr_mar_args& M
         }
     }
     if (ctx.tid == 0) {
-        M.kappa_hi[job] = hi;
-        if (M.kappa_lo) M.kappa_lo[job] = lo;
-        if (A.iters) A.iters[job] = total;
+        M.kappa_hi[out] = hi;
+        if (M.kappa_lo) M.kappa_lo[out] = lo;
+        if (A.iters) A.iters[out] = total;
     }
 }
 
 // ---- one-body arrangements: a lane per job ----------------------------------------------------------------------------------------------
-static UPR_HDI void upr_bal_margin_job1(const upr_mar_args& M, const upr_bal_dims& L, long long job) {
+template <bool GRP = false>
+static UPR_HDI void upr_bal_margin_job1(const upr_mar_args& M, const upr_bal_dims& L, long long job, long long out_grp = 0, unsigned mask = 0u,
+                                        const double* mu_base = nullptr) {
+    typedef upr_mar_src<GRP> SRC;
     const upr_bal_args& A = M.J;
     const upr_problem* P = A.P;
     const long long pt = job / A.n_scen;
     const int sc = (int)(job - pt * A.n_scen);
     const double* bp = A.params + (size_t)10 * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
-    double* zo = A.z ? A.z + (size_t)job * L.ncol : nullptr;
-    double* yo = M.y ? M.y + (size_t)job * 6 : nullptr;
+    const long long out = GRP ? out_grp : job;
+    const double* base = (GRP && mu_base) ? mu_base + (size_t)sc * P->nc : nullptr;
+    double* zo = A.z ? A.z + (size_t)out * L.ncol : nullptr;
+    double* yo = M.y ? M.y + (size_t)out * 6 : nullptr;
     double b[6];
     upr_bal_rhs1(P, A.st + (size_t)pt * UPR_BAL_ST, bp, A.eq_scale, b);
     double bb2 = 0.0;
@@ -155,7 +195,7 @@ static UPR_HDI void upr_bal_margin_job1(const upr_mar_args& M, const upr_bal_dim
         const double kap = (ev == 0) ? 0.0 : (ev == 1) ? M.kappa_max : 0.5 * (lo + hi);
         double r[6], zp[UPR_BAL1_MP], pc[UPR_BAL1_MP][6], G[UPR_BAL1_MP][UPR_BAL1_MP];
         int pidx[UPR_BAL1_MP], np;
-        const int it = upr_bal_project1(P, L, bp, A.eq_scale, kap, b, thr, r, zp, pidx, np, pc, G);
+        const int it = upr_bal_project1(P, L, bp, A.eq_scale, SRC::of(mask, base, kap), b, thr, r, zp, pidx, np, pc, G);
         total += it;
         double rr = 0.0;
         for (int c = 0; c < 6; ++c) rr += r[c] * r[c];
@@ -179,9 +219,34 @@ static UPR_HDI void upr_bal_margin_job1(const upr_mar_args& M, const upr_bal_dim
         }
     }
     if (hi == INFINITY && zo) for (int j = 0; j < L.ncol; ++j) zo[j] = 0.0;
-    M.kappa_hi[job] = hi;
-    if (M.kappa_lo) M.kappa_lo[job] = lo;
-    if (A.iters) A.iters[job] = total;
+    M.kappa_hi[out] = hi;
+    if (M.kappa_lo) M.kappa_lo[out] = lo;
+    if (A.iters) A.iters[out] = total;
+}
+
+// ---- the group margin: job jg = (point n_scen + scenario) n_grp + group of the wave form -------------------------------------------
+static UPR_HDI void upr_bal_margin_grp_job(const upr_ctx& ctx, const upr_grp_args& X, const upr_bal_dims& L, long long jg, double* W) {
+    const long long job = jg / X.n_grp;
+    upr_bal_margin_job<true>(ctx, X.M, L, job, W, jg, X.group_mask[(int)(jg - job * X.n_grp)], X.mu_base);
+}
+// the lane form: the group is uniform over the launch's waves (the mask stays in scalar registers)
+static UPR_HDI void upr_bal_margin_grp_job1(const upr_grp_args& X, const upr_bal_dims& L, long long job, int grp) {
+    upr_bal_margin_job1<true>(X.M, L, job, job * X.n_grp + grp, X.group_mask[grp], X.mu_base);
+}
+
+// ---- the largest kappa_hi over the knots of a plan ------------------------------------------------------------------------------------
+// kappa_hi [B][nk][inner] (inner = n_scen n_grp) -> worst [B][inner] and the first knot that attains it; +inf counts as largest.
+// One output per call, looping over the knots: no atomics.
+static UPR_HDI void upr_bal_margin_worst(const double* kappa_hi, int nk, long long inner, long long o, double* worst, int* knot) {
+    const long long b = o / inner, e = o - b * inner;
+    const double* src = kappa_hi + (size_t)b * nk * inner + e;
+    double w = src[0]; int kw = 0;
+    for (int k = 1; k < nk; ++k) {
+        const double v = src[(size_t)k * inner];
+        if (v > w) { w = v; kw = k; }
+    }
+    worst[o] = w;
+    if (knot) knot[o] = kw;
 }
 
 #ifndef UPR_HOST_EMU
@@ -195,5 +260,20 @@ __global__ __launch_bounds__(64) void upr_bal_margin_kernel(upr_mar_args M, upr_
 __global__ __launch_bounds__(64) void upr_bal_margin1_kernel(upr_mar_args M, upr_bal_dims L, long long njobs) {
     const long long job = (long long)blockIdx.x * 64 + threadIdx.x;
     if (job < njobs) upr_bal_margin_job1(M, L, job);
+}
+// the group margin, a wave per (job, group): njobs counts them
+__global__ __launch_bounds__(64) void upr_bal_margin_grp_kernel(upr_grp_args X, upr_bal_dims L, long long njobs) {
+    extern __shared__ double upr_bal_lds[];
+    upr_ctx ctx; ctx.tid = threadIdx.x; ctx.nt = 64;
+    for (long long jg = blockIdx.x; jg < njobs; jg += gridDim.x) upr_bal_margin_grp_job(ctx, X, L, jg, upr_bal_lds);
+}
+// one-body arrangements: a lane per (point, scenario) job, the group on blockIdx.y; njobs counts the (point, scenario) jobs
+__global__ __launch_bounds__(64) void upr_bal_margin1_grp_kernel(upr_grp_args X, upr_bal_dims L, long long njobs) {
+    const long long job = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (job < njobs) upr_bal_margin_grp_job1(X, L, job, (int)blockIdx.y);
+}
+__global__ __launch_bounds__(64) void upr_bal_margin_worst_kernel(const double* kappa_hi, int nk, long long inner, long long nout, double* worst, int* knot) {
+    const long long o = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (o < nout) upr_bal_margin_worst(kappa_hi, nk, inner, o, worst, knot);
 }
 #endif

@@ -291,7 +291,8 @@ class BatchMPC:
         want_z / want_iters the tuple (rho, z (n, n_scen, ncol), iters (n, n_scen)) restricted to what was asked for; z are the
         multipliers of the cone generators (balance_forces turns them into contact forces).  mu_scale (a number or one per scenario,
         finite and >= 0): every contact's friction coefficient is scaled by it in that scenario (the --mu of process_sim_runs.py as
-        a scenario axis, upr_batch_balance_points_mu); None and 1 give the same bits.
+        a scenario axis, upr_batch_balance_points_mu); None and 1 give the same bits.  mu_scale of shape (n_scen, nc): a scale per
+        scenario and contact (upr_batch_balance_points_cmu; every pair of objects its own friction, compute_minimum_mu.py:12-30).
 
         The study's sweep (upright_robust/scripts/planning_sim_loop.py:548-559,613-616: the centre of mass at the centre, the face
         centres and the vertices of its box, times three inertia scales = 45 scenarios) for a one-body arrangement:
@@ -317,8 +318,14 @@ class BatchMPC:
         rho = np.zeros((n, n_scen))
         z = np.zeros((n, n_scen, self.balance_columns)) if want_z else None
         iters = np.zeros((n, n_scen), dtype=np.int32) if want_iters else None
-        mu = self._mu_scale(mu_scale, n_scen)
-        check(self._lib.upr_batch_balance_points_mu(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, ptr(mu), ptr(rho), ptr(z), iptr(iters)))
+        if self._per_contact(mu_scale, n_scen):
+            mu = cont(mu_scale)
+            check(self._lib.upr_batch_balance_points_cmu(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, ptr(mu), ptr(rho), ptr(z),
+                                                         iptr(iters)))
+        else:
+            mu = self._mu_scale(mu_scale, n_scen)
+            check(self._lib.upr_batch_balance_points_mu(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, ptr(mu), ptr(rho), ptr(z),
+                                                        iptr(iters)))
         out = (rho,) + ((z,) if want_z else ()) + ((iters,) if want_iters else ())
         return out[0] if len(out) == 1 else out
 
@@ -328,6 +335,43 @@ class BatchMPC:
             return None
         return np.ascontiguousarray(np.broadcast_to(np.asarray(mu_scale, dtype=np.float64), (n_scen,)))
 
+    def _per_contact(self, mu_scale, n_scen):
+        """mu_scale of shape (n_scen, nc): a scale per scenario and contact (the _cmu entries); every other shape takes the entry it
+        always took."""
+        return mu_scale is not None and np.ndim(mu_scale) == 2 and np.shape(mu_scale) == (n_scen, self.problem.nc)
+
+    def contact_groups(self):
+        """Labels (nc,) of the contacts by their pair of objects (contact_body1, contact_body2), numbered in the order of first
+        occurrence: compute_contact_idx of upright_cmd/scripts/tools/compute_minimum_mu.py:12-30, the `groups` of friction_margin."""
+        P = self.problem
+        seen, labels = {}, np.zeros(P.nc, dtype=np.int64)
+        for i in range(P.nc):
+            labels[i] = seen.setdefault((int(P.contact_body1[i]), int(P.contact_body2[i])), len(seen))
+        return labels
+
+    def _group_masks(self, groups):
+        """groups: labels (nc,) (-1: in no group; groups numbered 0 .. max) or a list of index lists -> masks (n_grp,) uint32."""
+        nc = self.problem.nc
+        if len(groups) and np.ndim(groups[0]) == 0:
+            labels = np.asarray(groups)
+            if labels.shape != (nc,):
+                raise ValueError("groups: a label array needs one label per contact")
+            sets = [np.flatnonzero(labels == g) for g in range(int(labels.max()) + 1)] if labels.max() >= 0 else []
+        else:
+            sets = [np.asarray(g, dtype=np.int64).ravel() for g in groups]
+        masks = np.zeros(len(sets), dtype=np.uint32)
+        for g, idx in enumerate(sets):
+            if idx.size and (idx.min() < 0 or idx.max() >= 32):
+                raise ValueError("groups: contact indices must lie in 0 .. 31")
+            for i in idx:
+                masks[g] |= np.uint32(1) << np.uint32(i)
+        return masks
+
+    def _mu_base(self, mu_base, n_scen):
+        if mu_base is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(mu_base, dtype=np.float64), (n_scen, self.problem.nc)))
+
     def balance_check_plan(self, params=None, want_iters=False, mu_scale=None):
         """rho (B, N + 1, n_scen) at the knots of the current plan, evaluated where they lie on the device (upr_batch_balance_plan).
         params None: every instance against its own body parameters (n_scen = 1, the nominal check); (n_scen, nb, 10): the same
@@ -335,8 +379,12 @@ class BatchMPC:
         n_scen, per_instance, params = self._plan_params(params)
         rho = np.zeros((self.B, self.N + 1, n_scen))
         iters = np.zeros((self.B, self.N + 1, n_scen), dtype=np.int32) if want_iters else None
-        mu = self._mu_scale(mu_scale, n_scen)
-        check(self._lib.upr_batch_balance_plan_mu(self._h, n_scen, ptr(params), per_instance, ptr(mu), ptr(rho), iptr(iters)))
+        if self._per_contact(mu_scale, n_scen):
+            mu = cont(mu_scale)
+            check(self._lib.upr_batch_balance_plan_cmu(self._h, n_scen, ptr(params), per_instance, ptr(mu), ptr(rho), iptr(iters)))
+        else:
+            mu = self._mu_scale(mu_scale, n_scen)
+            check(self._lib.upr_batch_balance_plan_mu(self._h, n_scen, ptr(params), per_instance, ptr(mu), ptr(rho), iptr(iters)))
         return (rho, iters) if want_iters else rho
 
     def _plan_params(self, params):
@@ -348,7 +396,7 @@ class BatchMPC:
         params = params.reshape((self.B, -1, P.nb, 10) if per_instance else (-1, P.nb, 10))
         return (params.shape[1] if per_instance else params.shape[0]), per_instance, params
 
-    def friction_margin(self, x, params, kappa_max=8.0, want_lo=False, want_z=False, want_y=False, want_iters=False):
+    def friction_margin(self, x, params, kappa_max=8.0, want_lo=False, want_z=False, want_y=False, want_iters=False, groups=None, mu_base=None):
         """kappa* (n, n_scen): the friction margin of the robot states x (n, 3 nq) under the inertial parameters params (layouts of
         balance_check) -- the smallest common scale on the arrangement's friction coefficients at which balancing forces exist
         (upr_batch_friction_margin_points).  kappa* < 1: the state is balanced and 1 - kappa* of the friction could be lost;
@@ -363,7 +411,14 @@ class BatchMPC:
         Returns kappa* alone or the tuple (kappa*, kappa_lo, z, y, iters) restricted to what was asked for: kappa_lo (n, n_scen) the
         last infeasible scale; z (n, n_scen, ncol) >= 0 the generator multipliers at kappa* with |b + A(kappa*) z| inside the ball;
         y (n, n_scen, 6 nb) the residual at kappa_lo, a separating direction (y' a_j(kappa_lo) >= 0 for every generator, y' b > 0);
-        iters (n, n_scen) the least-squares solves over all evaluations."""
+        iters (n, n_scen) the least-squares solves over all evaluations.
+
+        groups (labels (nc,), -1: in no group -- contact_groups() gives them by pair of objects -- or a list of index lists; groups
+        may overlap): the margin of every contact group by itself (upr_batch_friction_margin_groups_points), which interface binds
+        the state.  kappa scales the friction of the group's contacts only; the others keep mu_base (a number, (nc,) or (n_scen,
+        nc); None: 1) times their coefficient.  Every result gains a trailing group axis: kappa* (n, n_scen, n_grp), z (n, n_scen,
+        n_grp, ncol), ...  kappa*_g = 0: the group's friction is not needed; inf: more friction on this group alone does not help.
+        groups=None is the common margin above."""
         P = self.problem
         x = cont(x).reshape(-1, self.nx)
         n = x.shape[0]
@@ -371,26 +426,64 @@ class BatchMPC:
         per_point = params.ndim == 4
         params = params.reshape((n, -1, P.nb, 10) if per_point else (-1, P.nb, 10))
         n_scen = params.shape[1] if per_point else params.shape[0]
-        hi = np.zeros((n, n_scen))
-        lo = np.zeros((n, n_scen)) if want_lo else None
-        z = np.zeros((n, n_scen, self.balance_columns)) if want_z else None
-        y = np.zeros((n, n_scen, 6 * P.nb)) if want_y else None
-        iters = np.zeros((n, n_scen), dtype=np.int32) if want_iters else None
-        check(self._lib.upr_batch_friction_margin_points(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, float(kappa_max),
-                                                         ptr(hi), ptr(lo), ptr(z), ptr(y), iptr(iters)))
+        masks = None if groups is None else self._group_masks(groups)
+        shape = (n, n_scen) if masks is None else (n, n_scen, len(masks))
+        hi = np.zeros(shape)
+        lo = np.zeros(shape) if want_lo else None
+        z = np.zeros(shape + (self.balance_columns,)) if want_z else None
+        y = np.zeros(shape + (6 * P.nb,)) if want_y else None
+        iters = np.zeros(shape, dtype=np.int32) if want_iters else None
+        if masks is None:
+            if mu_base is not None:
+                raise ValueError("mu_base needs groups")
+            check(self._lib.upr_batch_friction_margin_points(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, float(kappa_max),
+                                                             ptr(hi), ptr(lo), ptr(z), ptr(y), iptr(iters)))
+        else:
+            base = self._mu_base(mu_base, n_scen)
+            check(self._lib.upr_batch_friction_margin_groups_points(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, len(masks),
+                                                                    masks.ctypes.data_as(C.POINTER(C.c_uint)), ptr(base), float(kappa_max), ptr(hi),
+                                                                    ptr(lo), ptr(z), ptr(y), iptr(iters)))
         out = (hi,) + tuple(a for a in (lo, z, y, iters) if a is not None)
         return out[0] if len(out) == 1 else out
 
-    def friction_margin_plan(self, params=None, kappa_max=8.0, want_lo=False, want_iters=False):
+    def friction_margin_plan(self, params=None, kappa_max=8.0, want_lo=False, want_iters=False, groups=None, mu_base=None, worst=False):
         """kappa* (B, N + 1, n_scen) at the knots of the current plan, evaluated where they lie on the device
         (upr_batch_friction_margin_plan); params as in balance_check_plan, the quantity as in friction_margin.  With want_lo /
-        want_iters the tuple (kappa*, kappa_lo, iters) restricted to what was asked for."""
+        want_iters the tuple (kappa*, kappa_lo, iters) restricted to what was asked for.
+
+        groups, mu_base as in friction_margin (upr_batch_friction_margin_groups_plan): kappa* (B, N + 1, n_scen, n_grp).  worst=True
+        (with groups): instead of kappa* per knot the pair (worst (B, n_scen, n_grp), knot (B, n_scen, n_grp)) -- the largest kappa*
+        over the knots of every instance (inf counts as largest) and the first knot that attains it, reduced on the device; only
+        these are downloaded.  want_lo / want_iters are not available with it."""
         n_scen, per_instance, params = self._plan_params(params)
-        shape = (self.B, self.N + 1, n_scen)
+        if groups is None:
+            if mu_base is not None or worst:
+                raise ValueError("mu_base and worst need groups")
+            shape = (self.B, self.N + 1, n_scen)
+            hi = np.zeros(shape)
+            lo = np.zeros(shape) if want_lo else None
+            iters = np.zeros(shape, dtype=np.int32) if want_iters else None
+            check(self._lib.upr_batch_friction_margin_plan(self._h, n_scen, ptr(params), per_instance, float(kappa_max), ptr(hi), ptr(lo), iptr(iters)))
+            out = (hi,) + tuple(a for a in (lo, iters) if a is not None)
+            return out[0] if len(out) == 1 else out
+        masks = self._group_masks(groups)
+        base = self._mu_base(mu_base, n_scen)
+        shape = (self.B, self.N + 1, n_scen, len(masks))
+        if worst:
+            if want_lo or want_iters:
+                raise ValueError("worst=True returns the reduction alone")
+            w = np.zeros((self.B, n_scen, len(masks)))
+            knot = np.zeros((self.B, n_scen, len(masks)), dtype=np.int32)
+            check(self._lib.upr_batch_friction_margin_groups_plan(self._h, n_scen, ptr(params), per_instance, len(masks),
+                                                                  masks.ctypes.data_as(C.POINTER(C.c_uint)), ptr(base), float(kappa_max), None, None, None,
+                                                                  ptr(w), iptr(knot)))
+            return w, knot
         hi = np.zeros(shape)
         lo = np.zeros(shape) if want_lo else None
         iters = np.zeros(shape, dtype=np.int32) if want_iters else None
-        check(self._lib.upr_batch_friction_margin_plan(self._h, n_scen, ptr(params), per_instance, float(kappa_max), ptr(hi), ptr(lo), iptr(iters)))
+        check(self._lib.upr_batch_friction_margin_groups_plan(self._h, n_scen, ptr(params), per_instance, len(masks),
+                                                              masks.ctypes.data_as(C.POINTER(C.c_uint)), ptr(base), float(kappa_max), ptr(hi), ptr(lo),
+                                                              iptr(iters), None, None))
         out = (hi,) + tuple(a for a in (lo, iters) if a is not None)
         return out[0] if len(out) == 1 else out
 
