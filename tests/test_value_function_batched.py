@@ -11,6 +11,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import fb_check
 from kkt_check import friction_rows
 from test_emu import Emu, _case, _obstacle_case
 from upright_amd import _capi
@@ -327,7 +328,8 @@ def test_cost_to_go_kernel_source_against_the_host_module(arrangements, name):
     qp_objective / qp_slack_penalties on the primal-dual point of the same emulated QP: Pk, pk, J and X at every knot, for the
     headline (hard), both instances of the soft case, upright_robust's eight bodies (frictionless, softened equality and state
     boxes) and the bottle with collision rows.  Bound on Pk: 3x the measured disagreement (MEASURED_PK above, with the floor: the host
-    recursion against the dense condensation on the same inputs); on pk and J: rounding of their sums; X: exact."""
+    recursion against the dense condensation on the same inputs, itself held under eps cond(M) N); on pk and J: rounding of their sums;
+    X: exact.  The binding check of Pk is tests/test_vf_reference.py: every shape against a reference that is neither."""
     P, x0, way, xs, us, kernel = _ctg_cases(arrangements, name)
     B = x0.shape[0]
     e = Emu(P, B)
@@ -343,7 +345,13 @@ def test_cost_to_go_kernel_source_against_the_host_module(arrangements, name):
             worst[key] = max(worst[key], rel_err(dev[key][b], host[key]))
         E = friction_rows(P) if P.nf == 3 else np.zeros((0, P.nf * P.nc))
         V = dense_condensation(P, lin[b], sols[b], E, e.Df[b], pairs[b])
-        worst["floor"] = max(worst["floor"], np.abs(host["Pk"][0] - V).max() / np.abs(V).max())
+        floor = np.abs(host["Pk"][0] - V).max() / np.abs(V).max()
+        worst["floor"] = max(worst["floor"], floor)
+        # the floor is held too: two float64 routes to the same P_0 (a recursion of N stage solves, one condensed solve), each solve good
+        # to eps cond relative, with the stage systems' condition number as the dense reference computes it (fb_check: cond(M) per knot)
+        cond = fb_check.feedback_reference(P, lin[b], sols[b], E, e.Df[b], pairs=pairs[b])[2].max()
+        worst["floor_bound"] = max(worst.get("floor_bound", 0.0), np.finfo(float).eps * cond * P.N)
+        assert floor <= np.finfo(float).eps * cond * P.N, (b, floor, cond)
         assert np.abs(dev["Pk"][b] - np.swapaxes(dev["Pk"][b], 1, 2)).max() == 0.0
     print("cost-to-go kernel source vs host, %s: " % name + "  ".join("%s %.2e" % kv for kv in worst.items()))
     tol_pk = 3.0 * MEASURED_PK[name][0]
