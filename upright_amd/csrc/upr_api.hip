@@ -267,6 +267,16 @@ struct upr_ls_sel : upr_ls_choice {
     char name[128] = "";          // the instantiation, as rocprofv3 prints it (upr_batch_ls_kernel_name)
 };
 
+// ... and the form of its balance family (upr_balance.h, upr_margin.h; "balance family" further down)
+namespace {
+enum { BAL_LANE = 0, BAL_WAVE = 1 };
+struct upr_bal_choice {
+    upr_bal_dims L{};      // the layout of a job
+    size_t lds = 0;        // dynamic LDS of a workgroup of the wave form, bytes
+    int form = BAL_WAVE;   // BAL_LANE: a lane per job (one-body shapes); BAL_WAVE: a wave per job
+};
+}  // namespace
+
 struct upr_batch {
     upr_problem P;
     upr_dims d;
@@ -331,7 +341,7 @@ struct upr_batch {
     hipEvent_t bal_ev[2] = {nullptr, nullptr};
     double bal_ms = 0.0;
     void* bal_buf = nullptr; size_t bal_cap = 0;   // scratch of the balance-check calls, grown on demand, used for nothing else
-    bool bal_lane = true;   // one-body shapes on the lane-per-job kernel (UPR_BAL_FORM=0 at create: the wave-per-job kernel for them too; tests)
+    upr_bal_choice bal;   // the form of the balance family's kernels on this handle
     std::vector<hipEvent_t> ev_pool, ev_free;   // events in use (pairs, in launch order) / harvested ones waiting for reuse
     std::vector<int> ev_slot;
 };
@@ -809,128 +819,46 @@ int advance_impl(upr_batch* h) {
     return 0;
 }
 
-// ---- balance check (upr_balance.h): both entry points end here.  x_host: n states [n][3 nq] to upload, or NULL with dx already on
-// the device; params_host: parameter blocks to upload ([count][nb][10]) or NULL with dparams already on the device.  Everything is
-// enqueued on the handle's stream behind whatever is in flight and the one synchronisation is the last statement.  The scratch of
-// the calls is one block on the handle that serves nothing else and only grows (bal_buf: states, kernel outputs, uploaded
-// parameters and points): a call in the steady state allocates and frees nothing.
+// ---- balance family (upr_balance.h, upr_margin.h): the ten entry points end here, in balance_call.  An entry fills a REQUEST, which
+// names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
+// go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
+// the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
+// it carves the scratch block region by region, noting with every region what is copied into it before the kernels and out of it
+// after them, and takes the kernel from a table by form and quantity.  Everything is enqueued on the handle's stream behind
+// whatever is in flight and the one synchronisation is the last statement.  The scratch of the calls is one block on the handle
+// that serves nothing else and only grows (bal_buf): a call in the steady state allocates and frees nothing.
+enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
+enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2 };         // the quantity: the distance rho | the common friction margin | one per contact group
+struct bal_request {
+    const char* who = "";     // the entry, as its messages name it
+    const char* needs = "";   // ... and what they say about its required pointers
+    // the points: the knots of the handle's plan where they lie on the device, or n states x [n][3 nq] on the host
+    bool plan = false; int n = 0; const double* x = nullptr;
+    // the scenarios: parameter blocks on the host, [n_scen][nb][10] for all points or (per) a set of their own for every point /
+    // every instance of the plan.  NULL (plan, n_scen == 1): every instance against its own body parameters
+    int n_scen = 0; const double* params = nullptr; bool per = false;
+    // the friction scale of every scenario (BAL_RHO)
+    int scale = BAL_MU_NONE; const double* mu_scale = nullptr;
+    // the quantity.  The margins (upr_margin.h) run on the same jobs: out is kappa_hi, z the multipliers there, iters the solves
+    // over all evaluations.  Per group every output gains a trailing [n_grp]; mu_base: the scales of the contacts outside the group
+    // ([n_scen][nc]; NULL: ones)
+    int quantity = BAL_RHO; double kappa_max = 0.0; int n_grp = 1; const unsigned* group_mask = nullptr; const double* mu_base = nullptr;
+    // the answers on the host; all but the required ones may be NULL.  worst / worst_knot ([B][n_scen][n_grp]; plan, per group): the
+    // largest kappa_hi over the knots of an instance, reduced on the device; out may then be NULL and kappa_hi stays on the device
+    double* out = nullptr;   // rho | kappa_hi
+    double *kappa_lo = nullptr, *z = nullptr, *y = nullptr; int* iters = nullptr; double* worst = nullptr; int* worst_knot = nullptr;
+};
+long long bal_points(const upr_batch* h, const bal_request& r) { return r.plan ? (long long)h->B * (h->d.N + 1) : r.n; }
+size_t bal_param_sets(const upr_batch* h, const bal_request& r) { return (size_t)(r.per ? (r.plan ? h->B : r.n) : 1) * r.n_scen; }
+
 size_t bal_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// the next region of a scratch block of `total` bytes so far: its offset (a region that is not wanted takes no room)
+size_t bal_take(size_t& total, size_t bytes, bool wanted) { const size_t o = total; total += wanted ? bal_up(bytes) : 0; return o; }
 int balance_scratch(upr_batch* h, size_t bytes) {
     if (bytes <= h->bal_cap) return 0;
     if (h->bal_buf) { UPR_HIP(hipFree(h->bal_buf)); h->bal_buf = nullptr; h->bal_cap = 0; }
     UPR_HIP(hipMalloc(&h->bal_buf, bytes));
     h->bal_cap = bytes;
-    return 0;
-}
-int balance_check_params(const upr_batch* h, const double* params, size_t count) {
-    const int nb = h->d.nb;
-    for (size_t i = 0; i < count * nb; ++i)
-        if (!(params[10 * i] > 0) || !std::isfinite(params[10 * i])) return fail("balance check: every body of every scenario needs a positive finite mass");
-    return 0;
-}
-// mu_scale_host: the friction scale of every scenario ([n_scen]; with mu_per_contact [n_scen][nc]) or NULL: ones.  mar: NULL for the
-// rho calls; else the friction-margin call (upr_margin.h) on the same jobs -- rho is not written, z is the one at kappa_hi, iters the
-// solves over all evaluations.  grp (with mar): the margin of every contact group, outputs [n][n_scen][n_grp]; base the table of base
-// scales ([n_scen][nc]) or NULL; worst / worst_knot ([n / nk][n_scen][n_grp], either may be NULL): the largest kappa_hi over the nk
-// knots of an instance, reduced on the device; mar->hi may then be NULL and kappa_hi stays on the device.
-struct bal_margin_out { double kappa_max; double* hi; double* lo; double* y; };
-struct bal_group_in { int n_grp; const unsigned* mask; const double* base; double* worst; int* worst_knot; int nk; };
-int balance_run(upr_batch* h, long long n, const double* x_host, const double* dx, int n_scen, const double* params_host, size_t params_count,
-                const double* dparams, int pdiv, double* rho, double* z, int* iters, const double* mu_scale_host = nullptr,
-                const bal_margin_out* mar = nullptr, bool mu_per_contact = false, const bal_group_in* grp = nullptr) {
-    const upr_dims& d = h->d;
-    const upr_bal_dims L = upr_bal_layout(d.nb, d.nc, d.nf);
-    const long long njobs = n * n_scen, ng = grp ? grp->n_grp : 1, nout = njobs * ng;
-    if (n > (1ll << 31) - 64 || nout > (1ll << 36)) return fail("balance check: too many points");
-    const double* mu_host = grp ? grp->base : mu_scale_host;
-    const size_t mu_count = (size_t)n_scen * ((grp || mu_per_contact) ? d.nc : 1);
-    const bool want_worst = grp && (grp->worst || grp->worst_knot);
-    const long long nworst = want_worst ? (n / grp->nk) * n_scen * ng : 0;
-    const size_t o_st = 0, o_rho = o_st + bal_up(sizeof(double) * n * UPR_BAL_ST), o_z = o_rho + bal_up(sizeof(double) * nout),
-                 o_it = o_z + (z ? bal_up(sizeof(double) * nout * L.ncol) : 0), o_par = o_it + (iters ? bal_up(sizeof(int) * nout) : 0),
-                 o_x = o_par + (params_host ? bal_up(sizeof(double) * params_count * d.nb * 10) : 0),
-                 o_mu = o_x + (x_host ? bal_up(sizeof(double) * n * d.nx) : 0),
-                 o_lo = o_mu + (mu_host ? bal_up(sizeof(double) * mu_count) : 0),
-                 o_y = o_lo + ((mar && mar->lo) ? bal_up(sizeof(double) * nout) : 0),
-                 o_gm = o_y + ((mar && mar->y) ? bal_up(sizeof(double) * nout * L.m) : 0),
-                 o_w = o_gm + (grp ? bal_up(sizeof(unsigned) * ng) : 0),
-                 o_wk = o_w + bal_up(sizeof(double) * nworst),
-                 total = o_wk + bal_up(sizeof(int) * nworst);
-    if (balance_scratch(h, total)) return 1;
-    char* base = (char*)h->bal_buf;
-    double* dst = (double*)(base + o_st); double* drho = (double*)(base + o_rho); double* dz = (double*)(base + o_z); int* dit = (int*)(base + o_it);
-    double* dlo = (double*)(base + o_lo); double* dy = (double*)(base + o_y);
-    if (params_host) {
-        UPR_HIP(hipMemcpyAsync(base + o_par, params_host, sizeof(double) * params_count * d.nb * 10, hipMemcpyHostToDevice, h->stream));
-        dparams = (const double*)(base + o_par);
-    }
-    if (x_host) {
-        UPR_HIP(hipMemcpyAsync(base + o_x, x_host, sizeof(double) * n * d.nx, hipMemcpyHostToDevice, h->stream));
-        dx = (const double*)(base + o_x);
-    }
-    if (mu_host) UPR_HIP(hipMemcpyAsync(base + o_mu, mu_host, sizeof(double) * mu_count, hipMemcpyHostToDevice, h->stream));
-    if (grp) UPR_HIP(hipMemcpyAsync(base + o_gm, grp->mask, sizeof(unsigned) * ng, hipMemcpyHostToDevice, h->stream));
-    if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
-    UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
-    const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
-    if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
-    else hipLaunchKernelGGL(upr_bal_state_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
-    UPR_HIP(hipGetLastError());
-    upr_bal_args A;
-    A.P = h->dP; A.n = (int)n; A.n_scen = n_scen; A.st = dst; A.params = dparams; A.pdiv = pdiv; A.eq_scale = d.eq_scale;
-    A.rho = drho; A.z = z ? dz : nullptr; A.iters = iters ? dit : nullptr;
-    A.mu_scale = (mu_scale_host && !grp) ? (const double*)(base + o_mu) : nullptr;
-    upr_mar_args M;
-    if (mar) { M.J = A; M.J.rho = nullptr; M.kappa_max = mar->kappa_max; M.kappa_hi = drho; M.kappa_lo = mar->lo ? dlo : nullptr; M.y = mar->y ? dy : nullptr; }
-    upr_grp_args X;
-    if (grp) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = grp->base ? (const double*)(base + o_mu) : nullptr; }
-    // the wave-per-job kernels: jobs are dealt round robin to a grid that fills the device a few times over (a workgroup is one
-    // wave; its LDS, at most 26.4 KB, lets six of the largest shape share a CU inside the 160 KiB)
-    const dim3 lane_grid((unsigned)((njobs + 63) / 64)), wave_grid((unsigned)(njobs < 16384 ? njobs : 16384));
-    const size_t lds = (size_t)L.total * sizeof(double);
-    if (upr_bal_lane_form(d.nb) && h->bal_lane) {
-        if (grp) hipLaunchKernelGGL(upr_bal_margin1_grp_kernel, dim3(lane_grid.x, (unsigned)ng), dim3(64), 0, h->stream, X, L, njobs);
-        else if (mar) hipLaunchKernelGGL(upr_bal_margin1_kernel, lane_grid, dim3(64), 0, h->stream, M, L, njobs);
-        else if (A.mu_scale && mu_per_contact) hipLaunchKernelGGL(upr_bal_project1_cmu_kernel, lane_grid, dim3(64), 0, h->stream, A, L, njobs);
-        else if (A.mu_scale) hipLaunchKernelGGL(upr_bal_project1_mu_kernel, lane_grid, dim3(64), 0, h->stream, A, L, njobs);
-        else hipLaunchKernelGGL(upr_bal_project1_kernel, lane_grid, dim3(64), 0, h->stream, A, L, njobs);
-    } else {
-        if (grp) hipLaunchKernelGGL(upr_bal_margin_grp_kernel, dim3((unsigned)(nout < 16384 ? nout : 16384)), dim3(64), lds, h->stream, X, L, nout);
-        else if (mar) hipLaunchKernelGGL(upr_bal_margin_kernel, wave_grid, dim3(64), lds, h->stream, M, L, njobs);
-        else if (A.mu_scale && mu_per_contact) hipLaunchKernelGGL(upr_bal_project_cmu_kernel, wave_grid, dim3(64), lds, h->stream, A, L, njobs);
-        else if (A.mu_scale) hipLaunchKernelGGL(upr_bal_project_mu_kernel, wave_grid, dim3(64), lds, h->stream, A, L, njobs);
-        else hipLaunchKernelGGL(upr_bal_project_kernel, wave_grid, dim3(64), lds, h->stream, A, L, njobs);
-    }
-    UPR_HIP(hipGetLastError());
-    if (want_worst) {
-        hipLaunchKernelGGL(upr_bal_margin_worst_kernel, dim3((unsigned)((nworst + 63) / 64)), dim3(64), 0, h->stream, (const double*)drho, grp->nk,
-                           (long long)n_scen * ng, nworst, (double*)(base + o_w), grp->worst_knot ? (int*)(base + o_wk) : nullptr);
-        UPR_HIP(hipGetLastError());
-    }
-    UPR_HIP(hipEventRecord(h->bal_ev[1], h->stream));
-    double* hi_host = mar ? mar->hi : rho;
-    if (hi_host) UPR_HIP(hipMemcpyAsync(hi_host, drho, sizeof(double) * nout, hipMemcpyDeviceToHost, h->stream));
-    if (z) UPR_HIP(hipMemcpyAsync(z, dz, sizeof(double) * nout * L.ncol, hipMemcpyDeviceToHost, h->stream));
-    if (iters) UPR_HIP(hipMemcpyAsync(iters, dit, sizeof(int) * nout, hipMemcpyDeviceToHost, h->stream));
-    if (mar && mar->lo) UPR_HIP(hipMemcpyAsync(mar->lo, dlo, sizeof(double) * nout, hipMemcpyDeviceToHost, h->stream));
-    if (mar && mar->y) UPR_HIP(hipMemcpyAsync(mar->y, dy, sizeof(double) * nout * L.m, hipMemcpyDeviceToHost, h->stream));
-    if (want_worst && grp->worst) UPR_HIP(hipMemcpyAsync(grp->worst, base + o_w, sizeof(double) * nworst, hipMemcpyDeviceToHost, h->stream));
-    if (want_worst && grp->worst_knot) UPR_HIP(hipMemcpyAsync(grp->worst_knot, base + o_wk, sizeof(int) * nworst, hipMemcpyDeviceToHost, h->stream));
-    UPR_HIP(hipStreamSynchronize(h->stream));
-    float ms = 0.0f;
-    UPR_HIP(hipEventElapsedTime(&ms, h->bal_ev[0], h->bal_ev[1]));
-    h->bal_ms = ms;
-    return 0;
-}
-int balance_check_mu(const double* mu_scale, int n_scen) {
-    if (mu_scale) for (int s = 0; s < n_scen; ++s)
-        if (!(mu_scale[s] >= 0) || !std::isfinite(mu_scale[s])) return fail("balance check: every mu_scale must be finite and >= 0");
-    return 0;
-}
-// a scale per scenario and contact (mu_scale_c of the _cmu calls, mu_base of the group margin)
-int balance_check_cmu(const double* v, size_t count, const char* what) {
-    if (v) for (size_t i = 0; i < count; ++i)
-        if (!(v[i] >= 0) || !std::isfinite(v[i])) return fail(std::string("balance check: every ") + what + " must be finite and >= 0");
     return 0;
 }
 int balance_check_groups(const upr_batch* h, int n_grp, const unsigned* group_mask) {
@@ -944,9 +872,118 @@ int balance_check_groups(const upr_batch* h, int n_grp, const unsigned* group_ma
     }
     return 0;
 }
-int balance_check_kappa(double kappa_max) {
-    if (!(kappa_max > 0) || !std::isfinite(kappa_max)) return fail("friction margin: kappa_max must be finite and > 0");
+int balance_check_scales(const double* v, size_t count, const char* what) {
+    if (v) for (size_t i = 0; i < count; ++i)
+        if (!(v[i] >= 0) || !std::isfinite(v[i])) return fail(std::string("balance check: every ") + what + " must be finite and >= 0");
     return 0;
+}
+// 0: a request to launch; 1: refused (upr_last_error says why); 2: no points, nothing to do
+int balance_validate(const upr_batch* h, const bal_request& r) {
+    const upr_dims& d = h->d;
+    auto refuse = [&](const char* why) { return fail(std::string(r.who) + ": " + why); };
+    if (r.quantity != BAL_RHO && (!(r.kappa_max > 0) || !std::isfinite(r.kappa_max))) return fail("friction margin: kappa_max must be finite and > 0");
+    if (r.quantity == BAL_MARGIN_GROUPS && balance_check_groups(h, r.n_grp, r.group_mask)) return 1;
+    if (!r.plan && r.n <= 0) return 2;
+    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst)) return refuse(r.needs);
+    if (r.plan && !r.params) {
+        if (r.n_scen != 1) return refuse("params == NULL needs n_scen == 1 (every instance's own body parameters)");
+    } else if (r.n_scen < 1) return refuse("n_scen must be >= 1");
+    if (r.params) for (size_t i = 0, e = bal_param_sets(h, r) * d.nb; i < e; ++i)
+        if (!(r.params[10 * i] > 0) || !std::isfinite(r.params[10 * i])) return fail("balance check: every body of every scenario needs a positive finite mass");
+    if (balance_check_scales(r.mu_scale, (size_t)r.n_scen * (r.scale == BAL_MU_CONTACT ? d.nc : 1), "mu_scale")) return 1;
+    if (balance_check_scales(r.mu_base, (size_t)r.n_scen * d.nc, "mu_base")) return 1;
+    const long long n = bal_points(h, r);
+    if (n > (1ll << 31) - 64 || n * r.n_scen * r.n_grp > (1ll << 36)) return fail("balance check: too many points");
+    return 0;
+}
+
+// form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
+// group.  Every kernel takes (its record, upr_bal_dims, long long jobs); the record is upr_bal_args, upr_mar_args for the common
+// margin and upr_grp_args for the groups.
+const void* const bal_kernels[2][5] = {
+    /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
+                    (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel},
+    /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
+                    (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel}};
+struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
+
+int balance_launch(upr_batch* h, const bal_request& r) {
+    const upr_dims& d = h->d;
+    upr_bal_dims L = h->bal.L;
+    const bool wave = h->bal.form == BAL_WAVE, margin = r.quantity != BAL_RHO, groups = r.quantity == BAL_MARGIN_GROUPS;
+    const long long n = bal_points(h, r), njobs = n * r.n_scen, ng = r.n_grp, nout = njobs * ng;
+    const bool want_worst = r.worst || r.worst_knot;
+    const long long nworst = want_worst ? (long long)h->B * r.n_scen * ng : 0;
+    const double* scale_host = groups ? r.mu_base : r.mu_scale;
+    const size_t scale_count = (size_t)r.n_scen * ((groups || r.scale == BAL_MU_CONTACT) ? d.nc : 1);
+    // the scratch block, region by region, with what goes into a region before the kernels (from) and out of it after them (to)
+    bal_copy up[4], down[7];
+    int nup = 0, ndown = 0; size_t total = 0;
+    auto region = [&](size_t bytes, bool wanted, const void* from, void* to) {
+        const size_t o = bal_take(total, bytes, wanted);
+        if (wanted && from) up[nup++] = {o, const_cast<void*>(from), bytes};
+        if (wanted && to) down[ndown++] = {o, to, bytes};
+        return o;
+    };
+    const size_t o_st = region(sizeof(double) * n * UPR_BAL_ST, true, nullptr, nullptr);
+    const size_t o_rho = region(sizeof(double) * nout, true, nullptr, r.out);
+    const size_t o_z = region(sizeof(double) * nout * L.ncol, r.z != nullptr, nullptr, r.z);
+    const size_t o_it = region(sizeof(int) * nout, r.iters != nullptr, nullptr, r.iters);
+    const size_t o_par = region(sizeof(double) * bal_param_sets(h, r) * d.nb * 10, r.params != nullptr, r.params, nullptr);
+    const size_t o_x = region(sizeof(double) * n * d.nx, !r.plan, r.x, nullptr);
+    const size_t o_mu = region(sizeof(double) * scale_count, scale_host != nullptr, scale_host, nullptr);
+    const size_t o_lo = region(sizeof(double) * nout, r.kappa_lo != nullptr, nullptr, r.kappa_lo);
+    const size_t o_y = region(sizeof(double) * nout * L.m, r.y != nullptr, nullptr, r.y);
+    const size_t o_gm = region(sizeof(unsigned) * ng, groups, r.group_mask, nullptr);
+    const size_t o_w = region(sizeof(double) * nworst, want_worst, nullptr, r.worst);
+    const size_t o_wk = region(sizeof(int) * nworst, want_worst, nullptr, r.worst_knot);
+    if (balance_scratch(h, total)) return 1;
+    char* base = (char*)h->bal_buf;
+    for (int i = 0; i < nup; ++i) UPR_HIP(hipMemcpyAsync(base + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, h->stream));
+    if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
+    UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
+    const double* dx = r.plan ? h->xs : (const double*)(base + o_x);
+    double *dst = (double*)(base + o_st), *drho = (double*)(base + o_rho);
+    const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
+    if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
+    else hipLaunchKernelGGL(upr_bal_state_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
+    UPR_HIP(hipGetLastError());
+    upr_bal_args A;
+    A.P = h->dP; A.n = (int)n; A.n_scen = r.n_scen; A.st = dst; A.eq_scale = d.eq_scale;
+    A.params = r.params ? (const double*)(base + o_par) : h->body_params;
+    A.pdiv = r.plan ? ((r.per || !r.params) ? d.N + 1 : 0) : (r.per ? 1 : 0);   // points that share a parameter set
+    A.rho = drho; A.z = r.z ? (double*)(base + o_z) : nullptr; A.iters = r.iters ? (int*)(base + o_it) : nullptr;
+    A.mu_scale = r.mu_scale ? (const double*)(base + o_mu) : nullptr;
+    upr_mar_args M;
+    if (margin) {
+        M.J = A; M.J.rho = nullptr; M.kappa_max = r.kappa_max; M.kappa_hi = drho;
+        M.kappa_lo = r.kappa_lo ? (double*)(base + o_lo) : nullptr; M.y = r.y ? (double*)(base + o_y) : nullptr;
+    }
+    upr_grp_args X;
+    if (groups) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = r.mu_base ? (const double*)(base + o_mu) : nullptr; }
+    // lane form: 64 jobs per workgroup, the groups on the y axis.  Wave form: a workgroup is one wave and the jobs (for the groups:
+    // job x group) are dealt round robin to a grid that fills the device a few times over (its LDS, at most 26.4 KB, lets six of
+    // the largest shape share a CU inside the 160 KiB)
+    long long count = (wave && groups) ? nout : njobs;
+    const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
+    void* args[] = {groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
+    UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][margin ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
+    if (want_worst) {
+        hipLaunchKernelGGL(upr_bal_margin_worst_kernel, dim3((unsigned)((nworst + 63) / 64)), dim3(64), 0, h->stream, (const double*)drho, d.N + 1,
+                           (long long)r.n_scen * ng, nworst, (double*)(base + o_w), r.worst_knot ? (int*)(base + o_wk) : nullptr);
+        UPR_HIP(hipGetLastError());
+    }
+    UPR_HIP(hipEventRecord(h->bal_ev[1], h->stream));
+    for (int i = 0; i < ndown; ++i) UPR_HIP(hipMemcpyAsync(down[i].host, base + down[i].off, down[i].bytes, hipMemcpyDeviceToHost, h->stream));
+    UPR_HIP(hipStreamSynchronize(h->stream));
+    float ms = 0.0f;
+    UPR_HIP(hipEventElapsedTime(&ms, h->bal_ev[0], h->bal_ev[1]));
+    h->bal_ms = ms;
+    return 0;
+}
+int balance_call(upr_batch* h, const bal_request& r) {
+    if (const int v = balance_validate(h, r)) return v == 1;
+    return balance_launch(h, r);
 }
 
 }  // namespace
@@ -1042,7 +1079,12 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
         if (!h->lin_sel.kern || !h->ls_sel.kern) { fail("the planned linearisation / line-search form is not an instantiation of upr_launch_select.h's lists"); delete h; return nullptr; }
     }
     if (const char* e = getenv("UPR_QP_ORDER")) h->order_on = atoi(e) != 0;
-    if (const char* e = getenv("UPR_BAL_FORM")) h->bal_lane = atoi(e) != 0;
+    {   // ... and the form of its balance family (UPR_BAL_FORM=0: the wave form for the one-body shapes too; tests)
+        const char* e = getenv("UPR_BAL_FORM");
+        h->bal.L = upr_bal_layout(d.nb, d.nc, d.nf);
+        h->bal.lds = (size_t)h->bal.L.total * sizeof(double);
+        h->bal.form = (upr_bal_lane_form(d.nb) && !(e && atoi(e) == 0)) ? BAL_LANE : BAL_WAVE;
+    }
     auto bad = [&]() { upr_batch_destroy(h); return (upr_batch*)nullptr; };
     if (hipStreamCreate(&h->stream) != hipSuccess) { fail("hipStreamCreate failed"); return bad(); }
     if (hipMalloc((void**)&h->dP, sizeof(upr_problem)) != hipSuccess) { fail("hipMalloc failed"); return bad(); }
@@ -1631,42 +1673,22 @@ double upr_batch_value_function_ms(upr_batch* h) {
     return h->vf_ms;
 }
 
+// the balance family: every entry names its request ("balance family" above)
 int upr_batch_balance_points_mu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, const double* mu_scale,
                                 double* rho, double* z, int* iters) {
     UPR_ENTER(h);
-    if (n <= 0) return 0;
-    if (!x || !params || !rho) return fail("upr_batch_balance_points: x, params and rho must not be NULL");
-    if (n_scen < 1) return fail("upr_batch_balance_points: n_scen must be >= 1");
-    const size_t count = (size_t)(per_point ? n : 1) * n_scen;
-    if (balance_check_params(h, params, count) || balance_check_mu(mu_scale, n_scen)) return 1;
-    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, rho, z, iters, mu_scale);
+    return balance_call(h, {.who = "upr_batch_balance_points", .needs = "x, params and rho must not be NULL", .n = n, .x = x, .n_scen = n_scen,
+                            .params = params, .per = per_point != 0, .scale = mu_scale ? BAL_MU_SCENARIO : BAL_MU_NONE, .mu_scale = mu_scale,
+                            .out = rho, .z = z, .iters = iters});
 }
 int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double* rho, double* z, int* iters) {
     return upr_batch_balance_points_mu(h, n, x, n_scen, params, per_point, nullptr, rho, z, iters);
 }
 
-// the plan's knots: the jobs of both plan calls (rho, or with mar the friction margin)
-static int balance_plan_run(upr_batch* h, const char* who, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho,
-                            double* z, int* iters, const bal_margin_out* mar, bool mu_per_contact = false, const bal_group_in* grp = nullptr) {
-    const long long n = (long long)h->B * (h->d.N + 1);
-    const int nmu = mu_per_contact ? h->d.nc : 1;
-    if (!params) {   // the nominal check: every instance against its own body parameters
-        if (n_scen != 1) return fail(std::string(who) + ": params == NULL needs n_scen == 1 (every instance's own body parameters)");
-        if (balance_check_mu(mu_scale, nmu) || (grp && balance_check_cmu(grp->base, h->d.nc, "mu_base"))) return 1;
-        return balance_run(h, n, nullptr, h->xs, 1, nullptr, 0, h->body_params, h->d.N + 1, rho, z, iters, mu_scale, mar, mu_per_contact, grp);
-    }
-    if (n_scen < 1) return fail(std::string(who) + ": n_scen must be >= 1");
-    const size_t count = (size_t)(per_instance ? h->B : 1) * n_scen;
-    if (balance_check_params(h, params, count) || balance_check_mu(mu_scale, n_scen * nmu)) return 1;
-    if (grp && balance_check_cmu(grp->base, (size_t)n_scen * h->d.nc, "mu_base")) return 1;
-    return balance_run(h, n, nullptr, h->xs, n_scen, params, count, nullptr, per_instance ? h->d.N + 1 : 0, rho, z, iters, mu_scale, mar, mu_per_contact,
-                       grp);
-}
-
 int upr_batch_balance_plan_mu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho, int* iters) {
     UPR_ENTER(h);
-    if (!rho) return fail("upr_batch_balance_plan: rho must not be NULL");
-    return balance_plan_run(h, "upr_batch_balance_plan", n_scen, params, per_instance, mu_scale, rho, nullptr, iters, nullptr);
+    return balance_call(h, {.who = "upr_batch_balance_plan", .needs = "rho must not be NULL", .plan = true, .n_scen = n_scen, .params = params,
+                            .per = per_instance != 0, .scale = mu_scale ? BAL_MU_SCENARIO : BAL_MU_NONE, .mu_scale = mu_scale, .out = rho, .iters = iters});
 }
 int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double* rho, int* iters) {
     return upr_batch_balance_plan_mu(h, n_scen, params, per_instance, nullptr, rho, iters);
@@ -1675,66 +1697,49 @@ int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int p
 int upr_batch_friction_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double kappa_max,
                                      double* kappa_hi, double* kappa_lo, double* z, double* y, int* iters) {
     UPR_ENTER(h);
-    if (balance_check_kappa(kappa_max)) return 1;
-    if (n <= 0) return 0;
-    if (!x || !params || !kappa_hi) return fail("upr_batch_friction_margin_points: x, params and kappa_hi must not be NULL");
-    if (n_scen < 1) return fail("upr_batch_friction_margin_points: n_scen must be >= 1");
-    const size_t count = (size_t)(per_point ? n : 1) * n_scen;
-    if (balance_check_params(h, params, count)) return 1;
-    const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, y};
-    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, nullptr, z, iters, nullptr, &mar);
+    return balance_call(h, {.who = "upr_batch_friction_margin_points", .needs = "x, params and kappa_hi must not be NULL", .n = n, .x = x, .n_scen = n_scen,
+                            .params = params, .per = per_point != 0, .quantity = BAL_MARGIN, .kappa_max = kappa_max, .out = kappa_hi, .kappa_lo = kappa_lo,
+                            .z = z, .y = y, .iters = iters});
 }
 
 int upr_batch_friction_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double kappa_max, double* kappa_hi,
                                    double* kappa_lo, int* iters) {
     UPR_ENTER(h);
-    if (balance_check_kappa(kappa_max)) return 1;
-    if (!kappa_hi) return fail("upr_batch_friction_margin_plan: kappa_hi must not be NULL");
-    const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, nullptr};
-    return balance_plan_run(h, "upr_batch_friction_margin_plan", n_scen, params, per_instance, nullptr, nullptr, nullptr, iters, &mar);
+    return balance_call(h, {.who = "upr_batch_friction_margin_plan", .needs = "kappa_hi must not be NULL", .plan = true, .n_scen = n_scen, .params = params,
+                            .per = per_instance != 0, .quantity = BAL_MARGIN, .kappa_max = kappa_max, .out = kappa_hi, .kappa_lo = kappa_lo, .iters = iters});
 }
 
 int upr_batch_balance_points_cmu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, const double* mu_scale_c,
                                  double* rho, double* z, int* iters) {
     UPR_ENTER(h);
-    if (n <= 0) return 0;
-    if (!x || !params || !rho || !mu_scale_c) return fail("upr_batch_balance_points_cmu: x, params, mu_scale_c and rho must not be NULL");
-    if (n_scen < 1) return fail("upr_batch_balance_points_cmu: n_scen must be >= 1");
-    const size_t count = (size_t)(per_point ? n : 1) * n_scen;
-    if (balance_check_params(h, params, count) || balance_check_mu(mu_scale_c, n_scen * h->d.nc)) return 1;
-    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, rho, z, iters, mu_scale_c, nullptr, true);
+    return balance_call(h, {.who = "upr_batch_balance_points_cmu", .needs = "x, params, mu_scale_c and rho must not be NULL", .n = n, .x = x,
+                            .n_scen = n_scen, .params = params, .per = per_point != 0, .scale = BAL_MU_CONTACT, .mu_scale = mu_scale_c, .out = rho, .z = z,
+                            .iters = iters});
 }
 
 int upr_batch_balance_plan_cmu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale_c, double* rho, int* iters) {
     UPR_ENTER(h);
-    if (!rho || !mu_scale_c) return fail("upr_batch_balance_plan_cmu: mu_scale_c and rho must not be NULL");
-    return balance_plan_run(h, "upr_batch_balance_plan_cmu", n_scen, params, per_instance, mu_scale_c, rho, nullptr, iters, nullptr, true);
+    return balance_call(h, {.who = "upr_batch_balance_plan_cmu", .needs = "mu_scale_c and rho must not be NULL", .plan = true, .n_scen = n_scen,
+                            .params = params, .per = per_instance != 0, .scale = BAL_MU_CONTACT, .mu_scale = mu_scale_c, .out = rho, .iters = iters});
 }
 
 int upr_batch_friction_margin_groups_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, int n_grp,
                                             const unsigned* group_mask, const double* mu_base, double kappa_max, double* kappa_hi, double* kappa_lo,
                                             double* z, double* y, int* iters) {
     UPR_ENTER(h);
-    if (balance_check_kappa(kappa_max) || balance_check_groups(h, n_grp, group_mask)) return 1;
-    if (n <= 0) return 0;
-    if (!x || !params || !kappa_hi) return fail("upr_batch_friction_margin_groups_points: x, params and kappa_hi must not be NULL");
-    if (n_scen < 1) return fail("upr_batch_friction_margin_groups_points: n_scen must be >= 1");
-    const size_t count = (size_t)(per_point ? n : 1) * n_scen;
-    if (balance_check_params(h, params, count) || balance_check_cmu(mu_base, (size_t)n_scen * h->d.nc, "mu_base")) return 1;
-    const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, y};
-    const bal_group_in grp = {n_grp, group_mask, mu_base, nullptr, nullptr, 1};
-    return balance_run(h, n, x, nullptr, n_scen, params, count, nullptr, per_point ? 1 : 0, nullptr, z, iters, nullptr, &mar, false, &grp);
+    return balance_call(h, {.who = "upr_batch_friction_margin_groups_points", .needs = "x, params and kappa_hi must not be NULL", .n = n, .x = x,
+                            .n_scen = n_scen, .params = params, .per = per_point != 0, .quantity = BAL_MARGIN_GROUPS, .kappa_max = kappa_max, .n_grp = n_grp,
+                            .group_mask = group_mask, .mu_base = mu_base, .out = kappa_hi, .kappa_lo = kappa_lo, .z = z, .y = y, .iters = iters});
 }
 
 int upr_batch_friction_margin_groups_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_grp, const unsigned* group_mask,
                                           const double* mu_base, double kappa_max, double* kappa_hi, double* kappa_lo, int* iters, double* worst,
                                           int* worst_knot) {
     UPR_ENTER(h);
-    if (balance_check_kappa(kappa_max) || balance_check_groups(h, n_grp, group_mask)) return 1;
-    if (!kappa_hi && !worst) return fail("upr_batch_friction_margin_groups_plan: kappa_hi and worst must not both be NULL");
-    const bal_margin_out mar = {kappa_max, kappa_hi, kappa_lo, nullptr};
-    const bal_group_in grp = {n_grp, group_mask, mu_base, worst, worst_knot, h->d.N + 1};
-    return balance_plan_run(h, "upr_batch_friction_margin_groups_plan", n_scen, params, per_instance, nullptr, nullptr, nullptr, iters, &mar, false, &grp);
+    return balance_call(h, {.who = "upr_batch_friction_margin_groups_plan", .needs = "kappa_hi and worst must not both be NULL", .plan = true,
+                            .n_scen = n_scen, .params = params, .per = per_instance != 0, .quantity = BAL_MARGIN_GROUPS, .kappa_max = kappa_max,
+                            .n_grp = n_grp, .group_mask = group_mask, .mu_base = mu_base, .out = kappa_hi, .kappa_lo = kappa_lo, .iters = iters,
+                            .worst = worst, .worst_knot = worst_knot});
 }
 
 double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }

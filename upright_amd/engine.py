@@ -11,6 +11,12 @@ import numpy as np
 from . import _capi
 from ._capi import check, cont, iptr, ptr
 
+F8, I4 = np.float64, np.int32
+
+
+def uptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint))
+
 
 class BatchMPC:
     def __init__(self, problem, B=1, body_params=None, way_p=None, way_q=None, device=None):
@@ -308,25 +314,36 @@ class BatchMPC:
             rho = mpc.balance_check_plan(np.stack(params))    # (B, N + 1, 45)
             unsafe = (rho > 1e-6).any(axis=(1, 2))            # instances whose plan loses balance in some scenario
         """
+        x, n, params, n_scen, per_point = self._points_args(x, params)
+        rho, z, iters = self._outputs((n, n_scen), (True, (), F8), (want_z, (self.balance_columns,), F8), (want_iters, (), I4))
+        if self._per_contact(mu_scale, n_scen):
+            entry, mu = self._lib.upr_batch_balance_points_cmu, cont(mu_scale)
+        else:
+            entry, mu = self._lib.upr_batch_balance_points_mu, self._mu_scale(mu_scale, n_scen)
+        check(entry(self._h, n, ptr(x), n_scen, ptr(params), per_point, ptr(mu), ptr(rho), ptr(z), iptr(iters)))
+        return self._asked_for(rho, z, iters)
+
+    # -- what the balance family's methods share: the arguments of the points forms (the plan forms: _plan_params), the optional
+    # outputs and what is returned of them
+    def _points_args(self, x, params):
+        """x (n, 3 nq), n, params (n_scen, nb, 10) or per point (n, n_scen, nb, 10), n_scen, per_point 0 | 1"""
         P = self.problem
         x = cont(x).reshape(-1, self.nx)
         n = x.shape[0]
         params = cont(params)
-        per_point = params.ndim == 4
+        per_point = 1 if params.ndim == 4 else 0
         params = params.reshape((n, -1, P.nb, 10) if per_point else (-1, P.nb, 10))
-        n_scen = params.shape[1] if per_point else params.shape[0]
-        rho = np.zeros((n, n_scen))
-        z = np.zeros((n, n_scen, self.balance_columns)) if want_z else None
-        iters = np.zeros((n, n_scen), dtype=np.int32) if want_iters else None
-        if self._per_contact(mu_scale, n_scen):
-            mu = cont(mu_scale)
-            check(self._lib.upr_batch_balance_points_cmu(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, ptr(mu), ptr(rho), ptr(z),
-                                                         iptr(iters)))
-        else:
-            mu = self._mu_scale(mu_scale, n_scen)
-            check(self._lib.upr_batch_balance_points_mu(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, ptr(mu), ptr(rho), ptr(z),
-                                                        iptr(iters)))
-        out = (rho,) + ((z,) if want_z else ()) + ((iters,) if want_iters else ())
+        return x, n, params, (params.shape[1] if per_point else params.shape[0]), per_point
+
+    @staticmethod
+    def _outputs(shape, *specs):
+        """For every (wanted, trailing shape, dtype): zeros of shape + trailing shape, or None where it is not wanted."""
+        return [np.zeros(shape + tail, dtype=dtype) if wanted else None for wanted, tail, dtype in specs]
+
+    @staticmethod
+    def _asked_for(*arrays):
+        """The arrays that exist: the first alone, or the tuple of them."""
+        out = tuple(a for a in arrays if a is not None)
         return out[0] if len(out) == 1 else out
 
     @staticmethod
@@ -377,15 +394,13 @@ class BatchMPC:
         params None: every instance against its own body parameters (n_scen = 1, the nominal check); (n_scen, nb, 10): the same
         scenarios for every instance; (B, n_scen, nb, 10): per instance.  mu_scale as in balance_check."""
         n_scen, per_instance, params = self._plan_params(params)
-        rho = np.zeros((self.B, self.N + 1, n_scen))
-        iters = np.zeros((self.B, self.N + 1, n_scen), dtype=np.int32) if want_iters else None
+        rho, iters = self._outputs((self.B, self.N + 1, n_scen), (True, (), F8), (want_iters, (), I4))
         if self._per_contact(mu_scale, n_scen):
-            mu = cont(mu_scale)
-            check(self._lib.upr_batch_balance_plan_cmu(self._h, n_scen, ptr(params), per_instance, ptr(mu), ptr(rho), iptr(iters)))
+            entry, mu = self._lib.upr_batch_balance_plan_cmu, cont(mu_scale)
         else:
-            mu = self._mu_scale(mu_scale, n_scen)
-            check(self._lib.upr_batch_balance_plan_mu(self._h, n_scen, ptr(params), per_instance, ptr(mu), ptr(rho), iptr(iters)))
-        return (rho, iters) if want_iters else rho
+            entry, mu = self._lib.upr_batch_balance_plan_mu, self._mu_scale(mu_scale, n_scen)
+        check(entry(self._h, n_scen, ptr(params), per_instance, ptr(mu), ptr(rho), iptr(iters)))
+        return self._asked_for(rho, iters)
 
     def _plan_params(self, params):
         if params is None:
@@ -419,32 +434,20 @@ class BatchMPC:
         nc); None: 1) times their coefficient.  Every result gains a trailing group axis: kappa* (n, n_scen, n_grp), z (n, n_scen,
         n_grp, ncol), ...  kappa*_g = 0: the group's friction is not needed; inf: more friction on this group alone does not help.
         groups=None is the common margin above."""
-        P = self.problem
-        x = cont(x).reshape(-1, self.nx)
-        n = x.shape[0]
-        params = cont(params)
-        per_point = params.ndim == 4
-        params = params.reshape((n, -1, P.nb, 10) if per_point else (-1, P.nb, 10))
-        n_scen = params.shape[1] if per_point else params.shape[0]
+        x, n, params, n_scen, per_point = self._points_args(x, params)
         masks = None if groups is None else self._group_masks(groups)
-        shape = (n, n_scen) if masks is None else (n, n_scen, len(masks))
-        hi = np.zeros(shape)
-        lo = np.zeros(shape) if want_lo else None
-        z = np.zeros(shape + (self.balance_columns,)) if want_z else None
-        y = np.zeros(shape + (6 * P.nb,)) if want_y else None
-        iters = np.zeros(shape, dtype=np.int32) if want_iters else None
+        hi, lo, z, y, iters = self._outputs((n, n_scen) if masks is None else (n, n_scen, len(masks)), (True, (), F8), (want_lo, (), F8),
+                                            (want_z, (self.balance_columns,), F8), (want_y, (self.ne,), F8), (want_iters, (), I4))
         if masks is None:
             if mu_base is not None:
                 raise ValueError("mu_base needs groups")
-            check(self._lib.upr_batch_friction_margin_points(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, float(kappa_max),
+            check(self._lib.upr_batch_friction_margin_points(self._h, n, ptr(x), n_scen, ptr(params), per_point, float(kappa_max),
                                                              ptr(hi), ptr(lo), ptr(z), ptr(y), iptr(iters)))
         else:
             base = self._mu_base(mu_base, n_scen)
-            check(self._lib.upr_batch_friction_margin_groups_points(self._h, n, ptr(x), n_scen, ptr(params), 1 if per_point else 0, len(masks),
-                                                                    masks.ctypes.data_as(C.POINTER(C.c_uint)), ptr(base), float(kappa_max), ptr(hi),
-                                                                    ptr(lo), ptr(z), ptr(y), iptr(iters)))
-        out = (hi,) + tuple(a for a in (lo, z, y, iters) if a is not None)
-        return out[0] if len(out) == 1 else out
+            check(self._lib.upr_batch_friction_margin_groups_points(self._h, n, ptr(x), n_scen, ptr(params), per_point, len(masks), uptr(masks), ptr(base),
+                                                                    float(kappa_max), ptr(hi), ptr(lo), ptr(z), ptr(y), iptr(iters)))
+        return self._asked_for(hi, lo, z, y, iters)
 
     def friction_margin_plan(self, params=None, kappa_max=8.0, want_lo=False, want_iters=False, groups=None, mu_base=None, worst=False):
         """kappa* (B, N + 1, n_scen) at the knots of the current plan, evaluated where they lie on the device
@@ -459,33 +462,18 @@ class BatchMPC:
         if groups is None:
             if mu_base is not None or worst:
                 raise ValueError("mu_base and worst need groups")
-            shape = (self.B, self.N + 1, n_scen)
-            hi = np.zeros(shape)
-            lo = np.zeros(shape) if want_lo else None
-            iters = np.zeros(shape, dtype=np.int32) if want_iters else None
+            hi, lo, iters = self._outputs((self.B, self.N + 1, n_scen), (True, (), F8), (want_lo, (), F8), (want_iters, (), I4))
             check(self._lib.upr_batch_friction_margin_plan(self._h, n_scen, ptr(params), per_instance, float(kappa_max), ptr(hi), ptr(lo), iptr(iters)))
-            out = (hi,) + tuple(a for a in (lo, iters) if a is not None)
-            return out[0] if len(out) == 1 else out
+            return self._asked_for(hi, lo, iters)
         masks = self._group_masks(groups)
         base = self._mu_base(mu_base, n_scen)
-        shape = (self.B, self.N + 1, n_scen, len(masks))
-        if worst:
-            if want_lo or want_iters:
-                raise ValueError("worst=True returns the reduction alone")
-            w = np.zeros((self.B, n_scen, len(masks)))
-            knot = np.zeros((self.B, n_scen, len(masks)), dtype=np.int32)
-            check(self._lib.upr_batch_friction_margin_groups_plan(self._h, n_scen, ptr(params), per_instance, len(masks),
-                                                                  masks.ctypes.data_as(C.POINTER(C.c_uint)), ptr(base), float(kappa_max), None, None, None,
-                                                                  ptr(w), iptr(knot)))
-            return w, knot
-        hi = np.zeros(shape)
-        lo = np.zeros(shape) if want_lo else None
-        iters = np.zeros(shape, dtype=np.int32) if want_iters else None
-        check(self._lib.upr_batch_friction_margin_groups_plan(self._h, n_scen, ptr(params), per_instance, len(masks),
-                                                              masks.ctypes.data_as(C.POINTER(C.c_uint)), ptr(base), float(kappa_max), ptr(hi), ptr(lo),
-                                                              iptr(iters), None, None))
-        out = (hi,) + tuple(a for a in (lo, iters) if a is not None)
-        return out[0] if len(out) == 1 else out
+        if worst and (want_lo or want_iters):
+            raise ValueError("worst=True returns the reduction alone")
+        hi, lo, iters = self._outputs((self.B, self.N + 1, n_scen, len(masks)), (not worst, (), F8), (want_lo, (), F8), (want_iters, (), I4))
+        w, knot = self._outputs((self.B, n_scen, len(masks)), (worst, (), F8), (worst, (), I4))
+        check(self._lib.upr_batch_friction_margin_groups_plan(self._h, n_scen, ptr(params), per_instance, len(masks), uptr(masks), ptr(base),
+                                                              float(kappa_max), ptr(hi), ptr(lo), iptr(iters), ptr(w), iptr(knot)))
+        return self._asked_for(hi, lo, iters, w, knot)
 
     def balance_ms(self):
         """Device time (ms) of the kernel launches of the last balance check or friction margin (HIP events around them)."""
