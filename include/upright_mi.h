@@ -427,8 +427,37 @@ int upr_batch_friction_margin_groups_points(upr_batch* h, int n, const double* x
 int upr_batch_friction_margin_groups_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_grp,
                                           const unsigned* group_mask, const double* mu_base, double kappa_max, double* kappa_hi,
                                           double* kappa_lo, int* iters, double* worst, int* worst_knot);
-/* device time (ms) of the two kernel launches of the last balance check or friction margin on the handle, HIP events around them
- * (copies excluded) */
+/* ------------------------------------------------------------------------------------------------
+ * Speed margin (upright_amd/csrc/upr_speed.h): the interval of uniform replay speeds at which a state is balanced.  A trajectory
+ * replayed s times faster, q(t) -> q(s t), turns x = (q, v, a) into x_s = (q, s v, s^2 a); b(s) = b0 + s^2 (b1 - b0) and A does not
+ * depend on s, so rho is convex in s^2 and the balanced speeds form one interval.  A speed is accepted iff rho(x_s; theta) <= 1e-8
+ * max(|b(s)|, 1) (UPR_BAL_FEAS) on the cold projection of the rho calls, b(s) rebuilt from the scaled state at every evaluation.
+ *   Evaluations lie on the grid s_max k 2^-32; the nominal speed is the grid point floor(2^32 / s_max), s = 1 itself for a power of
+ *   two.  Rest and s_max first; both accepted: done.  Rest accepted: 32 halvings for the upper end.  Else a seed: the nominal speed,
+ *   else s_max, else a descent search on the slope r' (b1 - b0) (32 halvings without an accepted point: no speed is accepted); then
+ *   halvings of [0, seed] and, unless s_max is accepted, of [seed, s_max]: at most 3 + 3 * 32 evaluations.
+ *       speed[4]  s_lo: the smallest accepted speed found (0 if rest is accepted); s_lo_out: the largest rejected speed below it (0
+ *                 if none); s_hi: the largest accepted speed found (s_max if s_max is accepted); s_hi_out: the smallest rejected
+ *                 speed above it (+inf if s_max is accepted).  No speed accepted: +inf, 0, -inf, s_max.  A bisected end has
+ *                 |in - out| = s_max 2^-32; the reported ends are the accepted side.
+ *       z[2]      multipliers at s_lo and at s_hi: z >= 0 and |b(s) + A z| <= 1e-8 max(|b(s)|, 1) (zeros without an accepted end);
+ *       y[2]      the residual of the projection at s_lo_out and at s_hi_out: y' a_j >= 0 for every generator and y' b(s) > 0 (zeros
+ *                 without a rejected end);
+ *       iters     least-squares solves over all evaluations.
+ *   upr_batch_speed_margin_points  layouts of upr_batch_balance_points: speed[n][n_scen][4], z[n][n_scen][2][ncol] or NULL,
+ *       y[n][n_scen][2][6 nb] or NULL, iters[n][n_scen] or NULL.  Host pointers.
+ *   upr_batch_speed_margin_plan  the knots of the current plan on the device, as upr_batch_balance_plan: speed[B][N+1][n_scen][4] or
+ *       NULL, iters[B][N+1][n_scen] or NULL; window[B][n_scen][2] or NULL: the largest s_lo and the smallest s_hi over the knots,
+ *       reduced on the device, knot[B][n_scen][2] (or NULL) the first knot attaining each -- with speed NULL only the reductions are
+ *       downloaded; limit[B] or NULL: the largest s at which s v, s^2 a and s^3 u of every knot stay inside the velocity,
+ *       acceleration and jerk boxes of the problem (+inf for a plan at rest).  speed and window must not both be NULL.
+ *   s_max must be finite and > 1.  Scratch, timing and the state of the handle as the friction margin above. */
+int upr_batch_speed_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double s_max,
+                                  double* speed, double* z, double* y, int* iters);
+int upr_batch_speed_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double s_max, double* speed,
+                                int* iters, double* window, int* knot, double* limit);
+/* device time (ms) of the kernel launches of the last balance check, friction margin or speed margin on the handle, HIP events around
+ * them (copies excluded) */
 double upr_batch_balance_ms(upr_batch* h);
 
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):

@@ -475,8 +475,51 @@ class BatchMPC:
                                                               float(kappa_max), ptr(hi), ptr(lo), iptr(iters), ptr(w), iptr(knot)))
         return self._asked_for(hi, lo, iters, w, knot)
 
+    def speed_margin(self, x, params, s_max=4.0, want_out=False, want_z=False, want_y=False, want_iters=False):
+        """s (n, n_scen, 2) = (s_lo, s_hi): the interval of uniform replay speeds at which the robot states x (n, 3 nq) are balanced
+        under the inertial parameters params (layouts of balance_check; upr_batch_speed_margin_points).  Replaying a trajectory s
+        times faster turns a knot (q, v, a) into (q, s v, s^2 a); a speed counts as balanced when the distance rho there is <= 1e-8
+        max(|b|, 1), the rule of friction_margin.  s_lo = 0: balanced at rest; s_hi = s_max: balanced up to s_max; s_hi < 1: the
+        plan must be slowed down to s_hi of its speed; s_hi > 1: it could be s_hi times faster; s_lo > 0: the state NEEDS motion
+        (a tilted tray); (inf, -inf): no speed in [0, s_max] balances it.  Both ends are the accepted, conservative side of a
+        bracket of width s_max 2^-32.  s_max must be finite and > 1.
+
+        Returns s alone or the tuple (s, out, z, y, iters) restricted to what was asked for: out (n, n_scen, 2) = (s_lo_out,
+        s_hi_out) the rejected neighbours of the two ends (0 below an s_lo of 0, inf above an s_hi of s_max; (0, s_max) where no
+        speed is accepted); z (n, n_scen, 2, ncol) >= 0 the generator multipliers at s_lo and at s_hi; y (n, n_scen, 2, 6 nb) the
+        residuals at s_lo_out and s_hi_out, separating directions; iters (n, n_scen) the least-squares solves over all
+        evaluations (at most 3 + 3 * 32 of them)."""
+        x, n, params, n_scen, per_point = self._points_args(x, params)
+        speed, z, y, iters = self._outputs((n, n_scen), (True, (4,), F8), (want_z, (2, self.balance_columns), F8), (want_y, (2, self.ne), F8),
+                                           (want_iters, (), I4))
+        check(self._lib.upr_batch_speed_margin_points(self._h, n, ptr(x), n_scen, ptr(params), per_point, float(s_max), ptr(speed), ptr(z), ptr(y),
+                                                      iptr(iters)))
+        return self._asked_for(speed[..., 0::2].copy(), speed[..., 1::2].copy() if want_out else None, z, y, iters)
+
+    def speed_margin_plan(self, params=None, s_max=4.0, want_out=False, want_iters=False, window=False):
+        """s (B, N + 1, n_scen, 2) = (s_lo, s_hi) at the knots of the current plan, evaluated where they lie on the device
+        (upr_batch_speed_margin_plan); params as in balance_check_plan, the quantity as in speed_margin.  With want_out /
+        want_iters the tuple (s, out, iters) restricted to what was asked for.
+
+        window=True: instead of s per knot the triple (window (B, n_scen, 2), knot (B, n_scen, 2), limit (B,)) -- the largest s_lo
+        and the smallest s_hi over the knots of every instance (the speeds at which the WHOLE plan stays balanced in a scenario:
+        window[..., 0] <= s <= window[..., 1]), the first knot that attains each, and the largest speed at which s v, s^2 a and
+        s^3 u of every knot stay inside the velocity, acceleration and jerk bounds of the problem (inf for a plan at rest);
+        reduced on the device, only these are downloaded.  want_out / want_iters are not available with it."""
+        n_scen, per_instance, params = self._plan_params(params)
+        if window and (want_out or want_iters):
+            raise ValueError("window=True returns the reductions alone")
+        speed, iters = self._outputs((self.B, self.N + 1, n_scen), (not window, (4,), F8), (want_iters, (), I4))
+        w, knot = self._outputs((self.B, n_scen, 2), (window, (), F8), (window, (), I4))
+        limit = np.zeros(self.B) if window else None
+        check(self._lib.upr_batch_speed_margin_plan(self._h, n_scen, ptr(params), per_instance, float(s_max), ptr(speed), iptr(iters), ptr(w), iptr(knot),
+                                                    ptr(limit)))
+        if window:
+            return w, knot, limit
+        return self._asked_for(speed[..., 0::2].copy(), speed[..., 1::2].copy() if want_out else None, iters)
+
     def balance_ms(self):
-        """Device time (ms) of the kernel launches of the last balance check or friction margin (HIP events around them)."""
+        """Device time (ms) of the kernel launches of the last balance check, friction margin or speed margin (HIP events around them)."""
         return float(self._lib.upr_batch_balance_ms(self._h))
 
     def balance_forces(self, z):
