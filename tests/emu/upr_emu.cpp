@@ -17,6 +17,7 @@
 #include "../../upright_amd/csrc/upr_qp3_list.h"
 #include "../../upright_amd/csrc/upr_qp_select.h"
 #include "../../upright_amd/csrc/upr_launch_select.h"
+#include "../../upright_amd/csrc/upr_iface.h"
 
 template <int NQ, bool ORI>
 static void lin_all_o(const upr_lin_args& A);
@@ -275,6 +276,12 @@ int emu_ls_forms(int* out) {
 #undef EMU_X
     return n;
 }
+
+// the interface-state functions of upr_iface.h, as upr_api.hip calls them (tests/test_interface_states.py)
+void emu_iface_split(int nx, int n_dyn, const double* xf, int n, double* xr, double* dyn) { upr_iface_split(nx, n_dyn, xf, (size_t)n, xr, dyn); }
+void emu_iface_join(int nx, int n_dyn, const double* xr, const double* dyn, int n, double* out) { upr_iface_join(nx, n_dyn, xr, dyn, (size_t)n, out); }
+void emu_iface_join_zero(int nx, int n_dyn, const double* xr, int n, double* out) { upr_iface_join_zero(nx, n_dyn, xr, (size_t)n, out); }
+void emu_iface_join_ballistic(int nx, int n_dyn, const double* xr, const double* dyn, double tau, double* out) { upr_iface_join_ballistic(nx, n_dyn, xr, dyn, tau, out); }
 
 long emu_qp3_lds_doubles() { return (long)upr_qp3_lds<upr_qp3_cfg<9, 1, 4, 3, 20, 256>>::total; }
 

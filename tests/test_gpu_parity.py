@@ -2120,22 +2120,10 @@ def test_two_dynamic_obstacles(arrangements):
     state 27 + 18.  Against the oracle: the collision / projectile rows and their gradients through the C-ABI at random
     states, one MPC solve (linearise at every knot with both obstacles propagated ballistically, QP, line search), and
     the obstacle blocks of the returned trajectory are the ballistic continuations of what was observed."""
-    from test_emu import _projectile_case
-    from upright_amd import robots
+    from test_emu import _two_obstacle_case
 
     B = 3
-    P, x0r, way, xs0, us0, ball = _projectile_case(arrangements, B, use_feedback_policy=True)
-    pairs = [("wrist1_collision_link_0", "shoulder_collision_link_0"), ("wrist3_collision_link_0", "ground"),
-             ("base_collision_link_0", "chair1"), ("forearm_collision_sphere_link2_0", "projectile1"), ("balanced_object_collision_link_0", "chair1")]
-    for k, v in robots.collision_model(P.chain, pairs, dynamic={"chair1": 0.25, "projectile1": 0.2}).items():
-        setattr(P, k, v)
-    P.n_dyn = 2
-    P.proj_sph = np.zeros(0, dtype=np.int32); P.proj_dist = np.zeros(0)
-    robots.add_projectile_rows(P, ["balanced_object_collision_link"], [0.35], 0.2)
-    frames = list(P.sph_frame)
-    assert frames[list(P.sphere_names).index("chair1")] == -2 and frames[list(P.sphere_names).index("projectile1")] == -3
-    p0, _ = P.chain.forward(x0r[0, :9])
-    chair = np.tile(np.concatenate([p0 * [1, 1, 0] + [0.9, -0.5, 0.25], [0.0, 0.15, 0.0], np.zeros(3)]), (B, 1))   # drifting at 0.15 m/s
+    P, x0r, way, xs0, us0, chair, ball = _two_obstacle_case(arrangements, B, use_feedback_policy=True)
     x = np.concatenate([x0r, chair, ball], axis=1)
     assert x.shape[1] == P.nx_full == 45
     mpc = BatchMPC(P, B, way_p=way)

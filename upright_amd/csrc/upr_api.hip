@@ -36,6 +36,7 @@
 #include "upr_balance.h"
 #include "upr_margin.h"
 #include "upr_speed.h"
+#include "upr_iface.h"
 
 namespace {
 
@@ -276,6 +277,11 @@ struct upr_bal_choice {
     size_t lds = 0;        // dynamic LDS of a workgroup of the wave form, bytes
     int form = BAL_WAVE;   // BAL_LANE: a lane per job (one-body shapes); BAL_WAVE: a wave per job
 };
+// statistics and QP dispatch keys of a handle as the last advance left them, taken before a query solves one more QP on the handle
+// and put back behind it (snapshot_take / snapshot_put_back)
+struct upr_stats_snapshot {
+    std::vector<double> stats; std::vector<unsigned char> keys;
+};
 }  // namespace
 
 struct upr_batch {
@@ -300,7 +306,7 @@ struct upr_batch {
     // dynamic obstacle (n_dyn == 1): observed state per instance (device + host copies, and the one the stored
     // solution belongs to), activation flag of the projectile rows
     double *dyn0 = nullptr, *pflag = nullptr;
-    std::vector<double> hdyn0, hdyn_prev, htprev;
+    std::vector<double> hdyn0, hdyn_prev;
     double* pin = nullptr;   // pinned host staging of upr_batch_tick
     // upr_batch_tick as a HIP graph: the eleven stream operations of a control period (three copies in, prepare, linearise, QP,
     // line search, policy, three copies out) captured once the handle is in its steady state and replayed while that state --
@@ -324,7 +330,7 @@ struct upr_batch {
     double k_ms[3] = {0, 0, 0};
     int k_launches[3] = {0, 0, 0};
     std::vector<double> hDf;
-    std::vector<double> held_stats; std::vector<unsigned char> held_keys;   // upr_batch_hold_stats
+    upr_stats_snapshot held;   // upr_batch_hold_stats
     std::vector<double> kkt_slack;   // slacks of the rows at the exit of the last upr_batch_qp_kkt ([B][N+1][ni]; upr_batch_qp_slacks)
     std::vector<double> kkt_pairs;   // slack pairs of the softened rows of that QP, [3: sigma, tau, gam][B][N+1][ni] (upr_batch_qp_slack_pairs)
     // value function of the last QP (upr_batch_value_function_update): cost-to-go matrices, gradients, cost-to-go of the plan and
@@ -1003,6 +1009,42 @@ int balance_call(upr_batch* h, const bal_request& r) {
     return balance_launch(h, r);
 }
 
+// ---- what several entries share -------------------------------------------------------------------------------------------
+// the time of every instance: t[B], or one time for all (t_stride == 0)
+void instance_times(int B, const double* t, int t_stride, double* out) {
+    for (int b = 0; b < B; ++b) out[b] = t[(size_t)b * (t_stride ? 1 : 0)];
+}
+// scratch of the evaluate / evaluate_policy / tick calls (per-tick path of the closed loop: preallocated in the handle on first use)
+int eval_scratch(upr_batch* h) {
+    const size_t B = (size_t)h->B, nx = (size_t)h->d.nx, nu = (size_t)h->d.nu;
+    if (!h->ev_t && (dev_alloc(&h->ev_t, B) || dev_alloc(&h->ev_xo, B * nx) || dev_alloc(&h->ev_x, B * (nx + nu)))) return 1;
+    h->ev_u = h->ev_x + B * nx;   // (one block: a control period copies both out in one piece)
+    return 0;
+}
+// statistics and dispatch keys of a handle whose stream is idle, into a snapshot and back
+int snapshot_take(upr_batch* h, upr_stats_snapshot& s) {
+    s.stats.resize((size_t)h->B * UPR_NSTATS); s.keys.resize(((size_t)h->B + 3) & ~(size_t)3);
+    UPR_HIP(hipMemcpy(s.stats.data(), h->stats, sizeof(double) * s.stats.size(), hipMemcpyDeviceToHost));
+    UPR_HIP(hipMemcpy(s.keys.data(), h->iter_key, s.keys.size(), hipMemcpyDeviceToHost));
+    return 0;
+}
+int snapshot_put_back(upr_batch* h, const upr_stats_snapshot& s) {
+    UPR_HIP(hipMemcpy(h->stats, s.stats.data(), sizeof(double) * s.stats.size(), hipMemcpyHostToDevice));
+    UPR_HIP(hipMemcpy(h->iter_key, s.keys.data(), s.keys.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+// the points of a query (value function, multipliers, linearisation): instance and time of each, checked and on the device for the call
+struct point_upload {
+    DevBuf<int> inst; DevBuf<double> t;
+    int up(const upr_batch* h, int n, const int* hinst, const double* ht) {
+        for (int i = 0; i < n; ++i) if (hinst[i] < 0 || hinst[i] >= h->B) return fail("instance index out of range");
+        if (inst.alloc(n) || t.alloc(n)) return 1;
+        UPR_HIP(hipMemcpy(inst, hinst, sizeof(int) * n, hipMemcpyHostToDevice));
+        UPR_HIP(hipMemcpy(t, ht, sizeof(double) * n, hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1057,8 +1099,8 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
     upr_batch* h = new upr_batch();
     if (hipGetDevice(&h->device) != hipSuccess) { fail("hipGetDevice failed"); delete h; return nullptr; }
     h->P = *P; h->d = upr_make_dims(P); h->B = B;
-    h->nxf = h->d.nx + 9 * P->n_dyn;
-    h->hdyn0.assign((size_t)B * 9 * P->n_dyn, 0.0); h->hdyn_prev = h->hdyn0; h->htprev.assign(B, 0.0);
+    h->nxf = (int)upr_iface_width(h->d.nx, P->n_dyn);
+    h->hdyn0.assign((size_t)B * upr_iface_dyn_width(P->n_dyn), 0.0); h->hdyn_prev = h->hdyn0;
     const upr_dims& d = h->d;
     if (d.nx > UPR_LPK) { fail("nx exceeds the 32 tangent lanes of the linearisation kernel"); delete h; return nullptr; }
     {   // the QP kernel of this handle (upr_qp_select.h): planned from the problem and the knobs, a run-time instantiation made where the
@@ -1110,7 +1152,7 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
     if (dev_alloc(&h->body_params, (size_t)B * d.nb * 10) || dev_alloc(&h->way_p, (size_t)B * P->n_way * 3) || dev_alloc(&h->way_q, (size_t)B * P->n_way * 4) ||
         // (observation: time, state and the dynamic obstacles' states in ONE block, [t B][x B nx][dyn B 9 n_dyn] -- a control period
         //  copies it in one piece, upr_batch_tick)
-        dev_alloc(&h->t0, (((size_t)B + 1) & ~(size_t)1) + (size_t)B * d.nx + (size_t)B * 9 * P->n_dyn) || dev_alloc(&h->xs, (size_t)B * n1 * d.nx) || dev_alloc(&h->us, (size_t)B * d.N * d.nu) ||
+        dev_alloc(&h->t0, (((size_t)B + 1) & ~(size_t)1) + (size_t)B * d.nx + (size_t)B * upr_iface_dyn_width(P->n_dyn)) || dev_alloc(&h->xs, (size_t)B * n1 * d.nx) || dev_alloc(&h->us, (size_t)B * d.N * d.nu) ||
         dev_alloc(&h->xs_prev, (size_t)B * n1 * d.nx) || dev_alloc(&h->us_prev, (size_t)B * d.N * d.nu) || dev_alloc(&h->tprev, B) ||
         dev_alloc(&h->lin, (size_t)B * n1 * d.lin_stride) || dev_alloc(&h->Df, (size_t)B * d.ne * d.nfc) ||
         dev_alloc(&h->ws, (size_t)B * d.ws_stride) || dev_alloc(&h->stats, (size_t)B * UPR_NSTATS) || dev_alloc(&h->done, B) || dev_alloc(&h->order, B) || dev_alloc(&h->iter_key, ((size_t)B + 3) & ~(size_t)3) ||
@@ -1189,10 +1231,9 @@ int upr_batch_set_target_orientations(upr_batch* h, const double* way_q) {
 }
 
 static int set_observation_core(upr_batch* h, const double* t, int t_stride, const double* x) {
-    UPR_ENTER(h);
     if (h->vf_state && !h->vf_tracked) h->vf_state = 2;   // (a tracked cost-to-go belongs to the solve: valid until the next advance)
     std::vector<double> tt(h->B);
-    for (int b = 0; b < h->B; ++b) tt[b] = t[(size_t)b * (t_stride ? 1 : 0)];
+    instance_times(h->B, t, t_stride, tt.data());
     UPR_HIP(hipMemcpyAsync(h->t0, tt.data(), sizeof(double) * h->B, hipMemcpyHostToDevice, h->stream));
     UPR_HIP(hipMemcpyAsync(h->x0, x, sizeof(double) * h->B * h->d.nx, hipMemcpyHostToDevice, h->stream));
     UPR_HIP(hipStreamSynchronize(h->stream));
@@ -1200,7 +1241,6 @@ static int set_observation_core(upr_batch* h, const double* t, int t_stride, con
 }
 
 static int set_guess_core(upr_batch* h, const double* xs, const double* us) {
-    UPR_ENTER(h);
     if (h->vf_state) h->vf_state = 2;
     const upr_dims& d = h->d;
     UPR_HIP(hipMemcpyAsync(h->xs, xs, sizeof(double) * h->B * (d.N + 1) * d.nx, hipMemcpyHostToDevice, h->stream));
@@ -1238,7 +1278,6 @@ int upr_batch_advance(upr_batch* h) {
 }
 
 static int get_solution_core(upr_batch* h, double* ts, double* xs, double* us) {
-    UPR_ENTER(h);
     const upr_dims& d = h->d;
     UPR_HIP(hipStreamSynchronize(h->stream));
     if (ts) {
@@ -1251,34 +1290,18 @@ static int get_solution_core(upr_batch* h, double* ts, double* xs, double* us) {
     return 0;
 }
 
-static int evaluate_core(upr_batch* h, const double* t, int t_stride, double* x_out, double* u_out) {
-    UPR_ENTER(h);
+// the plan at the times t: evaluate, or (policy) evaluate_policy at the observed robot states x_obs[B][nx]
+static int evaluate_core(upr_batch* h, const double* t, int t_stride, bool policy, const double* x_obs, double* x_out, double* u_out) {
+    if (policy && !h->fb) return fail("upr_batch_evaluate_policy: the batch was created with use_feedback_policy = 0");
     const upr_dims& d = h->d;
-    // (per-tick path of the closed loop: scratch preallocated in the handle on first use)
-    if (!h->ev_t && (dev_alloc(&h->ev_t, h->B) || dev_alloc(&h->ev_xo, (size_t)h->B * d.nx) || dev_alloc(&h->ev_x, (size_t)h->B * (d.nx + d.nu)))) return 1;
-    h->ev_u = h->ev_x + (size_t)h->B * d.nx;   // (one block: a control period copies both out in one piece)
+    if (eval_scratch(h)) return 1;
     std::vector<double> tt(h->B);
-    for (int b = 0; b < h->B; ++b) tt[b] = t[(size_t)b * (t_stride ? 1 : 0)];
+    instance_times(h->B, t, t_stride, tt.data());
     UPR_HIP(hipMemcpyAsync(h->ev_t, tt.data(), sizeof(double) * h->B, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(evaluate_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->ev_t, 1, h->ev_x, h->ev_u);
-    UPR_HIP(hipGetLastError());
-    UPR_HIP(hipMemcpyAsync(x_out, h->ev_x, sizeof(double) * h->B * d.nx, hipMemcpyDeviceToHost, h->stream));
-    UPR_HIP(hipMemcpyAsync(u_out, h->ev_u, sizeof(double) * h->B * d.nu, hipMemcpyDeviceToHost, h->stream));
-    UPR_HIP(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-static int evaluate_policy_core(upr_batch* h, const double* t, int t_stride, const double* x_obs, double* x_out, double* u_out) {
-    UPR_ENTER(h);
-    if (!h->fb) return fail("upr_batch_evaluate_policy: the batch was created with use_feedback_policy = 0");
-    const upr_dims& d = h->d;
-    if (!h->ev_t && (dev_alloc(&h->ev_t, h->B) || dev_alloc(&h->ev_xo, (size_t)h->B * d.nx) || dev_alloc(&h->ev_x, (size_t)h->B * (d.nx + d.nu)))) return 1;
-    h->ev_u = h->ev_x + (size_t)h->B * d.nx;   // (one block: a control period copies both out in one piece)
-    std::vector<double> tt(h->B);
-    for (int b = 0; b < h->B; ++b) tt[b] = t[(size_t)b * (t_stride ? 1 : 0)];
-    UPR_HIP(hipMemcpyAsync(h->ev_t, tt.data(), sizeof(double) * h->B, hipMemcpyHostToDevice, h->stream));
-    UPR_HIP(hipMemcpyAsync(h->ev_xo, x_obs, sizeof(double) * h->B * d.nx, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(evaluate_policy_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->fb, h->ev_t, h->ev_xo, h->ev_x, h->ev_u);
+    if (policy) {
+        UPR_HIP(hipMemcpyAsync(h->ev_xo, x_obs, sizeof(double) * h->B * d.nx, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(evaluate_policy_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->fb, h->ev_t, h->ev_xo, h->ev_x, h->ev_u);
+    } else hipLaunchKernelGGL(evaluate_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->ev_t, 1, h->ev_x, h->ev_u);
     UPR_HIP(hipGetLastError());
     UPR_HIP(hipMemcpyAsync(x_out, h->ev_x, sizeof(double) * h->B * d.nx, hipMemcpyDeviceToHost, h->stream));
     UPR_HIP(hipMemcpyAsync(u_out, h->ev_u, sizeof(double) * h->B * d.nu, hipMemcpyDeviceToHost, h->stream));
@@ -1287,7 +1310,6 @@ static int evaluate_policy_core(upr_batch* h, const double* t, int t_stride, con
 }
 
 static int get_feedback_core(upr_batch* h, double* K) {
-    UPR_ENTER(h);
     if (!h->fb) return fail("upr_batch_get_feedback: the batch was created with use_feedback_policy = 0");
     const upr_dims& d = h->d;
     UPR_HIP(hipStreamSynchronize(h->stream));
@@ -1315,18 +1337,11 @@ const char* upr_batch_lin_kernel_name(upr_batch* h) {
  * upr_batch_get_stats and the longest-first dispatch order describe the SOLVE again, not the query's QP. */
 int upr_batch_hold_stats(upr_batch* h, int restore) {
     UPR_ENTER(h);
-    const size_t ns = sizeof(double) * h->B * UPR_NSTATS, nk = ((size_t)h->B + 3) & ~(size_t)3;
     UPR_HIP(hipStreamSynchronize(h->stream));
-    if (!restore) {
-        h->held_stats.resize((size_t)h->B * UPR_NSTATS); h->held_keys.resize(nk);
-        UPR_HIP(hipMemcpy(h->held_stats.data(), h->stats, ns, hipMemcpyDeviceToHost));
-        UPR_HIP(hipMemcpy(h->held_keys.data(), h->iter_key, nk, hipMemcpyDeviceToHost));
-        return 0;
-    }
-    if (h->held_stats.empty()) return fail("upr_batch_hold_stats: nothing held on this handle");
-    UPR_HIP(hipMemcpy(h->stats, h->held_stats.data(), ns, hipMemcpyHostToDevice));
-    UPR_HIP(hipMemcpy(h->iter_key, h->held_keys.data(), nk, hipMemcpyHostToDevice));
-    h->held_stats.clear(); h->held_keys.clear();
+    if (!restore) return snapshot_take(h, h->held);
+    if (h->held.stats.empty()) return fail("upr_batch_hold_stats: nothing held on this handle");
+    if (snapshot_put_back(h, h->held)) return 1;
+    h->held = upr_stats_snapshot();
     return 0;
 }
 
@@ -1337,24 +1352,28 @@ int upr_batch_get_stats(upr_batch* h, double* stats) {
     return 0;
 }
 
-// points mode of the linearisation kernel: records of n arbitrary (x, u) pairs back on the host
-static int linearize_points_impl(upr_batch* h, int n, const int* inst, const double* t, const double* x, const double* u,
-                                 std::vector<double>& rec, double* ee, const double* dyn_pts = nullptr) {
+// points mode of the linearisation kernel: records of n arbitrary (x, u) pairs, x[n][nxf] interface states, back on the host
+static int linearize_points_impl(upr_batch* h, int n, const int* inst, const double* t, const double* x, const double* u, std::vector<double>& rec, double* ee) {
     const upr_dims& d = h->d;
-    for (int i = 0; i < n; ++i) if (inst[i] < 0 || inst[i] >= h->B) return fail("instance index out of range");
-    DevBuf<int> dinst; DevBuf<double> dt_, dx, du, dlin, dee, ddyn;
-    if (dinst.alloc(n) || dt_.alloc(n) || dx.alloc((size_t)n * d.nx) || du.alloc((size_t)n * d.nu) ||
-        dlin.alloc((size_t)n * d.lin_stride) || dee.alloc((size_t)n * 3)) return 1;
-    UPR_HIP(hipMemcpy(dinst, inst, sizeof(int) * n, hipMemcpyHostToDevice));
-    UPR_HIP(hipMemcpy(dt_, t, sizeof(double) * n, hipMemcpyHostToDevice));
+    const size_t nd = upr_iface_dyn_width(h->P.n_dyn);
+    point_upload pts;
+    if (pts.up(h, n, inst, t)) return 1;
+    std::vector<double> xr, dyn;
+    if (h->P.n_dyn) {   // interface states: the robot block is the point, the obstacle block the obstacles' state at that point
+        xr.resize((size_t)n * d.nx); dyn.resize((size_t)n * nd);
+        upr_iface_split(d.nx, h->P.n_dyn, x, (size_t)n, xr.data(), dyn.data());
+        x = xr.data();
+    }
+    DevBuf<double> dx, du, dlin, dee, ddyn;
+    if (dx.alloc((size_t)n * d.nx) || du.alloc((size_t)n * d.nu) || dlin.alloc((size_t)n * d.lin_stride) || dee.alloc((size_t)n * 3)) return 1;
     UPR_HIP(hipMemcpy(dx, x, sizeof(double) * n * d.nx, hipMemcpyHostToDevice));
     UPR_HIP(hipMemcpy(du, u, sizeof(double) * n * d.nu, hipMemcpyHostToDevice));
     upr_lin_args A;
-    A.P = h->dP; A.d = d; A.body_params = h->body_params; A.way_p = h->way_p; A.way_q = upr_has_orientation_cost(&h->P) ? h->way_q : nullptr; A.t0 = dt_; A.xs = dx; A.us = du; A.inst = dinst;
+    A.P = h->dP; A.d = d; A.body_params = h->body_params; A.way_p = h->way_p; A.way_q = upr_has_orientation_cost(&h->P) ? h->way_q : nullptr; A.t0 = pts.t; A.xs = dx; A.us = du; A.inst = pts.inst;
     A.lin = dlin; A.ee_out = dee; A.npoints = n; A.Df = h->Df;
     if (h->P.n_dyn) {   // points mode: the obstacle state of every point as given
-        if (ddyn.alloc((size_t)n * 9 * h->P.n_dyn)) return 1;
-        if (dyn_pts) UPR_HIP(hipMemcpy(ddyn, dyn_pts, sizeof(double) * n * 9 * h->P.n_dyn, hipMemcpyHostToDevice));
+        if (ddyn.alloc((size_t)n * nd)) return 1;
+        UPR_HIP(hipMemcpy(ddyn, dyn.data(), sizeof(double) * n * nd, hipMemcpyHostToDevice));
         A.dyn = ddyn; A.pflag = h->pflag;
     }
     if (launch_linearize(h, A)) return 1;
@@ -1370,17 +1389,8 @@ int upr_batch_linearize_points(upr_batch* h, int n, const int* inst, const doubl
     UPR_ENTER(h);
     if (n <= 0) return 0;
     const upr_dims& d = h->d;
-    std::vector<double> rec, xr, dyn;
-    if (h->P.n_dyn) {   // interface states [robot x, obstacle]; Jacobian outputs keep the 3 nq robot columns
-        const size_t nd9 = 9 * (size_t)h->P.n_dyn;
-        xr.resize((size_t)n * d.nx); dyn.resize((size_t)n * nd9);
-        for (int i = 0; i < n; ++i) {
-            std::memcpy(xr.data() + (size_t)i * d.nx, x + (size_t)i * h->nxf, sizeof(double) * d.nx);
-            std::memcpy(dyn.data() + (size_t)i * nd9, x + (size_t)i * h->nxf + d.nx, sizeof(double) * nd9);
-        }
-        x = xr.data();
-    }
-    if (linearize_points_impl(h, n, inst, t, x, u, rec, ee, h->P.n_dyn ? dyn.data() : nullptr)) return 1;
+    std::vector<double> rec;
+    if (linearize_points_impl(h, n, inst, t, x, u, rec, ee)) return 1;   // (Jacobian outputs keep the 3 nq robot columns)
     for (int i = 0; i < n; ++i) {
         const double* r = rec.data() + (size_t)i * d.lin_stride;
         if (g) std::memcpy(g + (size_t)i * d.ne, r + d.lin_g, sizeof(double) * d.ne);
@@ -1395,12 +1405,8 @@ int upr_batch_linearize_points(upr_batch* h, int n, const int* inst, const doubl
 // the first `nr` state rows (slot order of the record) at n points (inst[n], t[n], interface states x[n][nx_full]): d[n][nr], dq[n][nr][nq]
 static int state_rows_impl(upr_batch* h, int n, const int* inst, const double* t, const double* x, int nr, double* dd, double* dq) {
     const upr_dims& d = h->d;
-    std::vector<double> u((size_t)n * d.nu, 0.0), rec, xr((size_t)n * d.nx), dyn((size_t)n * 9 * h->P.n_dyn);
-    for (int i = 0; i < n; ++i) {   // interface states: [robot x, obstacle r v a]
-        std::memcpy(xr.data() + (size_t)i * d.nx, x + (size_t)i * h->nxf, sizeof(double) * d.nx);
-        if (h->P.n_dyn) std::memcpy(dyn.data() + (size_t)i * 9 * h->P.n_dyn, x + (size_t)i * h->nxf + d.nx, sizeof(double) * 9 * h->P.n_dyn);
-    }
-    if (linearize_points_impl(h, n, inst, t, xr.data(), u.data(), rec, nullptr, h->P.n_dyn ? dyn.data() : nullptr)) return 1;
+    std::vector<double> u((size_t)n * d.nu, 0.0), rec;
+    if (linearize_points_impl(h, n, inst, t, x, u.data(), rec, nullptr)) return 1;
     for (int i = 0; i < n; ++i) {
         const double* r = rec.data() + (size_t)i * d.lin_stride + d.lin_obs;
         std::memcpy(dd + (size_t)i * nr, r, sizeof(double) * nr);
@@ -1424,8 +1430,7 @@ int upr_batch_state_rows(upr_batch* h, int n, const int* inst, const double* t, 
     const upr_dims& d = h->d;
     if (d.no == 0) return fail("upr_batch_state_rows: the problem has no state rows");
     if (n <= 0) return 0;
-    for (int i = 0; i < n; ++i) if (inst[i] < 0 || inst[i] >= h->B) return fail("instance index out of range");
-    return state_rows_impl(h, n, inst, t, x, d.no, dd, dq);
+    return state_rows_impl(h, n, inst, t, x, d.no, dd, dq);   // (inst is checked where it is uploaded: point_upload)
 }
 
 int upr_batch_eq_input_jacobian(upr_batch* h, int inst, double* gu) {
@@ -1449,7 +1454,6 @@ static int kkt_launch(upr_batch* h) {
 }
 
 static int qp_step_core(upr_batch* h, double* dxs, double* dus) {
-    UPR_ENTER(h);
     const upr_dims& d = h->d;
     if (launch_linearize(h, traj_lin_args(h))) return 1;
     if (launch_qp(h, make_qp_args(h))) return 1;
@@ -1467,9 +1471,9 @@ static int qp_step_core(upr_batch* h, double* dxs, double* dus) {
 /* One QP at the current trajectory with everything an independent KKT check needs: the step and the multipliers the
  * kernel ended with.  pi[B][N+1][nx] costates (pi_0 unused), nu[B][N][ne] stage-equality multipliers, yN[B][neN]
  * terminal-equality multipliers, lam[B][N+1][ni] inequality multipliers, ni = 2 nx + 2 nu + np + no in the slot order
- * [x lower][x upper][u lower][u upper][friction rows][collision / projectile rows]; *ni_out = ni.  Any pointer may be NULL. */
-int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double* nu, double* yN, double* lam, int* ni_out) {
-    UPR_ENTER(h);
+ * [x lower][x upper][u lower][u upper][friction rows][collision / projectile rows]; *ni_out = ni.  Any pointer may be NULL.
+ * (upr_batch_qp_kkt, "interface states" further down: dxs in robot width here, as qp_step_core's) */
+static int qp_kkt_core(upr_batch* h, double* dxs, double* dus, double* pi, double* nu, double* yN, double* lam, int* ni_out) {
     const upr_dims& d = h->d;
     if (ni_out) *ni_out = d.ni_stage;
     const upr_qp_sel& sel = h->qp;   // (where the selected kernel left the primal-dual point: the export buffer or the workspace)
@@ -1481,12 +1485,7 @@ int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double*
     const int n1 = d.N + 1;
     for (int b = 0; b < h->B; ++b) {
         const double* w = ws.data() + (size_t)b * d.ws_stride;
-        if (dxs && !h->P.n_dyn) std::memcpy(dxs + (size_t)b * n1 * d.nx, w + d.ws_dx, sizeof(double) * n1 * d.nx);
-        else if (dxs) for (int k = 0; k < n1; ++k) {   // interface width: the obstacle is data of the QP, its step is zero (upr_batch_qp_step)
-            double* o = dxs + ((size_t)b * n1 + k) * h->nxf;
-            std::memcpy(o, w + d.ws_dx + (size_t)k * d.nx, sizeof(double) * d.nx);
-            for (int c = d.nx; c < h->nxf; ++c) o[c] = 0.0;
-        }
+        if (dxs) std::memcpy(dxs + (size_t)b * n1 * d.nx, w + d.ws_dx, sizeof(double) * n1 * d.nx);
         if (dus) std::memcpy(dus + (size_t)b * d.N * d.nu, w + d.ws_du, sizeof(double) * d.N * d.nu);
         const size_t nsl = (size_t)n1 * d.ni_stage;
         const double* m = (sel.exported ? kk.data() : ws.data()) + (size_t)b * sel.stride;
@@ -1549,13 +1548,11 @@ int upr_batch_value_function_update_interface(upr_batch* h) {
     if (lds > 160 * 1024) return fail("upr_batch_value_function_update: working set exceeds 160 KiB of LDS");
     if (vf_alloc(h)) return 1;
     h->vf_state = 0; h->vf_tracked = false; h->vf_ms_pending = false;
-    // statistics and dispatch keys of the solve are put back behind the query's QP (what upr_batch_hold_stats does, on a copy of
-    // its own: a caller may hold one across this call)
-    const size_t ns = sizeof(double) * B * UPR_NSTATS, nk = (B + 3) & ~(size_t)3;
-    std::vector<double> st(B * UPR_NSTATS); std::vector<unsigned char> keys(nk);
+    // statistics and dispatch keys of the solve are put back behind the query's QP (what upr_batch_hold_stats does, on a snapshot
+    // of its own: a caller may hold the handle's across this call)
+    upr_stats_snapshot solve;
     UPR_HIP(hipStreamSynchronize(h->stream));
-    UPR_HIP(hipMemcpy(st.data(), h->stats, ns, hipMemcpyDeviceToHost));
-    UPR_HIP(hipMemcpy(keys.data(), h->iter_key, nk, hipMemcpyDeviceToHost));
+    if (snapshot_take(h, solve)) return 1;
     if (kkt_launch(h)) return 1;
     const upr_vf_args A = make_vf_args(h);
     if (lds > 64 * 1024) UPR_HIP(vf_raise_lds_limit());
@@ -1568,8 +1565,7 @@ int upr_batch_value_function_update_interface(upr_batch* h) {
     float ms = 0.0f;
     UPR_HIP(hipEventElapsedTime(&ms, h->vf_ev[0], h->vf_ev[1]));
     h->vf_ms = ms;
-    UPR_HIP(hipMemcpy(h->stats, st.data(), ns, hipMemcpyHostToDevice));
-    UPR_HIP(hipMemcpy(h->iter_key, keys.data(), nk, hipMemcpyHostToDevice));
+    if (snapshot_put_back(h, solve)) return 1;
     h->vf_state = 1;
     return 0;
 }
@@ -1607,27 +1603,24 @@ int upr_batch_track_value_function(upr_batch* h, int on) {
     return 0;
 }
 
-static void narrow_states(const upr_batch* h, const double* xf, size_t n, std::vector<double>& xr);
-
 int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double* t, const double* x, double* V, double* dVdx) {
     UPR_ENTER(h);
     if (vf_ready(h, "upr_batch_value_function")) return 1;
     if (n <= 0) return 0;
     if (!inst || !t || !x) return fail("upr_batch_value_function: null argument");
     const upr_dims& d = h->d;
-    for (int i = 0; i < n; ++i) if (inst[i] < 0 || inst[i] >= h->B) return fail("instance index out of range");
-    DevBuf<int> dinst; DevBuf<double> dt_, dx, dV, dg;
-    if (dinst.alloc(n) || dt_.alloc(n) || dx.alloc((size_t)n * d.nx) || dV.alloc(n) || dg.alloc((size_t)n * d.nx)) return 1;
-    UPR_HIP(hipMemcpy(dinst, inst, sizeof(int) * n, hipMemcpyHostToDevice));
-    UPR_HIP(hipMemcpy(dt_, t, sizeof(double) * n, hipMemcpyHostToDevice));
-    if (!h->P.n_dyn) UPR_HIP(hipMemcpy(dx, x, sizeof(double) * n * d.nx, hipMemcpyHostToDevice));
-    else {   // interface states: the robot block is what the expansion is in
-        std::vector<double> xr;
-        narrow_states(h, x, (size_t)n, xr);
-        UPR_HIP(hipMemcpy(dx, xr.data(), sizeof(double) * n * d.nx, hipMemcpyHostToDevice));
+    point_upload pts;
+    if (pts.up(h, n, inst, t)) return 1;
+    DevBuf<double> dx, dV, dg;
+    if (dx.alloc((size_t)n * d.nx) || dV.alloc(n) || dg.alloc((size_t)n * d.nx)) return 1;
+    std::vector<double> xr(h->P.n_dyn ? (size_t)n * d.nx : 0);
+    if (h->P.n_dyn) {   // interface states: the robot block is what the expansion is in
+        upr_iface_split(d.nx, h->P.n_dyn, x, (size_t)n, xr.data(), nullptr);
+        x = xr.data();
     }
+    UPR_HIP(hipMemcpy(dx, x, sizeof(double) * n * d.nx, hipMemcpyHostToDevice));
     upr_vfq_args A;
-    A.d = d; A.dt = h->P.dt; A.n = n; A.inst = dinst; A.t = dt_; A.x = dx; A.t0 = h->vf_t0;
+    A.d = d; A.dt = h->P.dt; A.n = n; A.inst = pts.inst; A.t = pts.t; A.x = dx; A.t0 = h->vf_t0;
     A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X; A.V = dV; A.dV = dg;
     hipLaunchKernelGGL(upr_value_query_kernel, dim3(n), dim3(64), 0, h->stream, A);
     UPR_HIP(hipGetLastError());
@@ -1637,10 +1630,7 @@ int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double*
     else if (dVdx) {   // the obstacle is data of the QP, not a state of its Riccati recursion: zero block
         std::vector<double> gr((size_t)n * d.nx);
         UPR_HIP(hipMemcpy(gr.data(), dg, sizeof(double) * gr.size(), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i) {
-            std::memcpy(dVdx + (size_t)i * h->nxf, gr.data() + (size_t)i * d.nx, sizeof(double) * d.nx);
-            for (int c = d.nx; c < h->nxf; ++c) dVdx[(size_t)i * h->nxf + c] = 0.0;
-        }
+        upr_iface_join_zero(d.nx, h->P.n_dyn, gr.data(), (size_t)n, dVdx);
     }
     return 0;
 }
@@ -1652,13 +1642,12 @@ int upr_batch_equality_lagrangian(upr_batch* h, int n, const int* inst, const do
     if (n <= 0) return 0;
     if (!inst || !t || !nu_out) return fail("upr_batch_equality_lagrangian: null argument");
     const upr_dims& d = h->d;
-    for (int i = 0; i < n; ++i) if (inst[i] < 0 || inst[i] >= h->B) return fail("instance index out of range");
-    DevBuf<int> dinst; DevBuf<double> dt_, dn;
-    if (dinst.alloc(n) || dt_.alloc(n) || dn.alloc((size_t)n * d.ne)) return 1;
-    UPR_HIP(hipMemcpy(dinst, inst, sizeof(int) * n, hipMemcpyHostToDevice));
-    UPR_HIP(hipMemcpy(dt_, t, sizeof(double) * n, hipMemcpyHostToDevice));
+    point_upload pts;
+    if (pts.up(h, n, inst, t)) return 1;
+    DevBuf<double> dn;
+    if (dn.alloc((size_t)n * d.ne)) return 1;
     upr_vfq_args A;
-    A.d = d; A.dt = h->P.dt; A.n = n; A.inst = dinst; A.t = dt_; A.x = nullptr; A.t0 = h->vf_t0;
+    A.d = d; A.dt = h->P.dt; A.n = n; A.inst = pts.inst; A.t = pts.t; A.x = nullptr; A.t0 = h->vf_t0;
     A.Pk = h->vf_P; A.pk = h->vf_p; A.J = h->vf_J; A.X = h->vf_X; A.V = nullptr; A.dV = nullptr;
     A.nu = h->vf_nu; A.nu_q = dn;
     hipLaunchKernelGGL(upr_value_query_kernel, dim3(n), dim3(64), 0, h->stream, A);
@@ -1874,34 +1863,32 @@ int upr_batch_reset_async(upr_batch* h) {
 }
 
 
-// ---- interface states: [robot x (3 nq), dynamic obstacle r v a (9 n_dyn)] ------------------------------------------------
-// The kernels work on the robot state; the obstacle is uncontrolled (system_dynamics.h:29-39), so its part of every
-// trajectory is the ballistic continuation of its observed state.  With n_dyn == 0 these wrappers are pass-throughs.
-static void narrow_states(const upr_batch* h, const double* xf, size_t n, std::vector<double>& xr) {
-    xr.resize(n * h->d.nx);
-    for (size_t i = 0; i < n; ++i) std::memcpy(xr.data() + i * h->d.nx, xf + i * h->nxf, sizeof(double) * h->d.nx);
-}
-static void obstacle_after(const double* xo, double tau, double* out, int n_dyn = 1) {   // every obstacle of an instance: [n_dyn][9]
-    for (int o = 0; o < n_dyn; ++o, xo += 9, out += 9)
-        for (int i = 0; i < 3; ++i) { out[6 + i] = xo[6 + i]; out[3 + i] = xo[3 + i] + tau * xo[6 + i]; out[i] = xo[i] + tau * xo[3 + i] + 0.5 * tau * tau * xo[6 + i]; }
-}
-
+// ---- interface states: [robot x (3 nq) | r v a of every dynamic obstacle (9 n_dyn)], width nxf --------------------------------
+// The kernels work on the robot state; the obstacles are uncontrolled (system_dynamics.h:29-39), so their part of every trajectory
+// is the ballistic continuation of what was observed.  With n_dyn == 0 the entries hand the caller's pointers to their cores.
+// Otherwise the layout is upr_iface.h's business:
+//   upr_iface_split           what comes IN.  The obstacle block goes to hdyn0 (set_observation, tick), is the obstacles' state at
+//                             the point (linearize_points, state_rows, obstacle_rows) or is ignored (set_guess, x_obs, value_function)
+//   upr_iface_join_zero       what goes OUT as a function of the robot state alone: qp_step, qp_kkt (dx), get_feedback, dV/dx
+//   upr_iface_join_ballistic  states that go OUT.  get_solution continues hdyn0, the LAST observation (the one the trajectory on the
+//                             device is for), by k dt; evaluate(_policy) continue hdyn_prev, the observation the STORED solution
+//                             belongs to (advance_impl copies hdyn0 there), by max(t - tprev, 0)
+// tick returns the obstacle block as observed (upr_iface_join): its policy is evaluated at the observation's own time.
 int upr_batch_set_observation(upr_batch* h, const double* t, int t_stride, const double* x) {
     UPR_ENTER(h);
     if (!h->P.n_dyn) return set_observation_core(h, t, t_stride, x);
-    std::vector<double> xr;
-    narrow_states(h, x, h->B, xr);
-    const size_t nd9 = 9 * (size_t)h->P.n_dyn;
-    for (int b = 0; b < h->B; ++b) std::memcpy(h->hdyn0.data() + (size_t)b * nd9, x + (size_t)b * h->nxf + h->d.nx, sizeof(double) * nd9);
-    UPR_HIP(hipMemcpy(h->dyn0, h->hdyn0.data(), sizeof(double) * h->B * nd9, hipMemcpyHostToDevice));
+    std::vector<double> xr((size_t)h->B * h->d.nx);
+    upr_iface_split(h->d.nx, h->P.n_dyn, x, (size_t)h->B, xr.data(), h->hdyn0.data());
+    UPR_HIP(hipMemcpy(h->dyn0, h->hdyn0.data(), sizeof(double) * h->hdyn0.size(), hipMemcpyHostToDevice));
     return set_observation_core(h, t, t_stride, xr.data());
 }
 
 int upr_batch_set_guess(upr_batch* h, const double* xs, const double* us) {
     UPR_ENTER(h);
     if (!h->P.n_dyn) return set_guess_core(h, xs, us);
-    std::vector<double> xr;
-    narrow_states(h, xs, (size_t)h->B * (h->d.N + 1), xr);
+    const size_t n = (size_t)h->B * (h->d.N + 1);
+    std::vector<double> xr(n * h->d.nx);
+    upr_iface_split(h->d.nx, h->P.n_dyn, xs, n, xr.data(), nullptr);
     return set_guess_core(h, xr.data(), us);
 }
 
@@ -1909,44 +1896,36 @@ int upr_batch_get_solution(upr_batch* h, double* ts, double* xs, double* us) {
     UPR_ENTER(h);
     if (!h->P.n_dyn || !xs) return get_solution_core(h, ts, xs, us);
     const upr_dims& d = h->d;
-    std::vector<double> xr((size_t)h->B * (d.N + 1) * d.nx);
+    const size_t n1 = (size_t)d.N + 1, nd = upr_iface_dyn_width(h->P.n_dyn);
+    std::vector<double> xr((size_t)h->B * n1 * d.nx);
     if (get_solution_core(h, ts, xr.data(), us)) return 1;
-    for (int b = 0; b < h->B; ++b) for (int k = 0; k <= d.N; ++k) {
-        double* o = xs + ((size_t)b * (d.N + 1) + k) * h->nxf;
-        std::memcpy(o, xr.data() + ((size_t)b * (d.N + 1) + k) * d.nx, sizeof(double) * d.nx);
-        obstacle_after(h->hdyn0.data() + (size_t)b * 9 * h->P.n_dyn, k * h->P.dt, o + d.nx, h->P.n_dyn);
-    }
+    for (size_t b = 0; b < (size_t)h->B; ++b) for (size_t k = 0; k < n1; ++k)
+        upr_iface_join_ballistic(d.nx, h->P.n_dyn, xr.data() + (b * n1 + k) * d.nx, h->hdyn0.data() + b * nd, (int)k * h->P.dt, xs + (b * n1 + k) * h->nxf);
     return 0;
 }
 
-static void widen_eval(upr_batch* h, const double* t, int t_stride, const double* xr, double* x_out) {
-    std::vector<double> tp(h->B);
-    (void)hipMemcpy(tp.data(), h->tprev, sizeof(double) * h->B, hipMemcpyDeviceToHost);
-    for (int b = 0; b < h->B; ++b) {
-        double* o = x_out + (size_t)b * h->nxf;
-        std::memcpy(o, xr + (size_t)b * h->d.nx, sizeof(double) * h->d.nx);
-        double tau = t[(size_t)b * (t_stride ? 1 : 0)] - tp[b];
-        obstacle_after(h->hdyn_prev.data() + (size_t)b * 9 * h->P.n_dyn, tau > 0.0 ? tau : 0.0, o + h->d.nx, h->P.n_dyn);
+// evaluate and (policy) evaluate_policy
+static int evaluate_iface(upr_batch* h, const double* t, int t_stride, bool policy, const double* x_obs, double* x_out, double* u_out) {
+    if (!h->P.n_dyn) return evaluate_core(h, t, t_stride, policy, x_obs, x_out, u_out);
+    const size_t B = (size_t)h->B, nx = (size_t)h->d.nx, nd = upr_iface_dyn_width(h->P.n_dyn);
+    std::vector<double> xo(policy ? B * nx : 0), xr(B * nx), tp(B), tt(B);
+    if (policy) upr_iface_split(h->d.nx, h->P.n_dyn, x_obs, B, xo.data(), nullptr);
+    if (evaluate_core(h, t, t_stride, policy, xo.data(), xr.data(), u_out)) return 1;
+    UPR_HIP(hipMemcpy(tp.data(), h->tprev, sizeof(double) * B, hipMemcpyDeviceToHost));
+    instance_times(h->B, t, t_stride, tt.data());
+    for (size_t b = 0; b < B; ++b) {
+        const double tau = tt[b] - tp[b];
+        upr_iface_join_ballistic(h->d.nx, h->P.n_dyn, xr.data() + b * nx, h->hdyn_prev.data() + b * nd, tau > 0.0 ? tau : 0.0, x_out + b * h->nxf);
     }
+    return 0;
 }
-
 int upr_batch_evaluate(upr_batch* h, const double* t, int t_stride, double* x_out, double* u_out) {
     UPR_ENTER(h);
-    if (!h->P.n_dyn) return evaluate_core(h, t, t_stride, x_out, u_out);
-    std::vector<double> xr((size_t)h->B * h->d.nx);
-    if (evaluate_core(h, t, t_stride, xr.data(), u_out)) return 1;
-    widen_eval(h, t, t_stride, xr.data(), x_out);
-    return 0;
+    return evaluate_iface(h, t, t_stride, false, nullptr, x_out, u_out);
 }
-
 int upr_batch_evaluate_policy(upr_batch* h, const double* t, int t_stride, const double* x_obs, double* x_out, double* u_out) {
     UPR_ENTER(h);
-    if (!h->P.n_dyn) return evaluate_policy_core(h, t, t_stride, x_obs, x_out, u_out);
-    std::vector<double> xo, xr((size_t)h->B * h->d.nx);
-    narrow_states(h, x_obs, h->B, xo);
-    if (evaluate_policy_core(h, t, t_stride, xo.data(), xr.data(), u_out)) return 1;
-    widen_eval(h, t, t_stride, xr.data(), x_out);
-    return 0;
+    return evaluate_iface(h, t, t_stride, true, x_obs, x_out, u_out);
 }
 
 int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x, double* x_out, double* u_out, double* stats_out) {
@@ -1954,9 +1933,8 @@ int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x,
     if (!t || !x || !x_out || !u_out) return fail("upr_batch_tick: null argument");
     if (h->vf_state) h->vf_state = 2;
     const upr_dims& d = h->d;
-    const size_t B = (size_t)h->B, nx = (size_t)d.nx, nu = (size_t)d.nu, ndyn = 9 * (size_t)h->P.n_dyn;
-    if (!h->ev_t && (dev_alloc(&h->ev_t, h->B) || dev_alloc(&h->ev_xo, B * nx) || dev_alloc(&h->ev_x, B * (nx + nu)))) return 1;
-    h->ev_u = h->ev_x + B * nx;
+    const size_t B = (size_t)h->B, nx = (size_t)d.nx, nu = (size_t)d.nu, ndyn = upr_iface_dyn_width(h->P.n_dyn);
+    if (eval_scratch(h)) return 1;
     // pinned staging: [t B (+ pad)][x B nx][dyn B 9 n_dyn] in (the layout of the device block h->t0), [x B nx][u B nu][stats B NSTATS] out
     const size_t Bt = (B + 1) & ~(size_t)1;   // (the block of times is padded to an even count, as on the device)
     const size_t n_in = Bt + B * nx + B * ndyn, n_out = B * nx + B * nu + B * UPR_NSTATS;
@@ -1965,11 +1943,9 @@ int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x,
     }
     double* pt = h->pin; double* px = pt + Bt; double* pd = px + B * nx;
     double* ox = h->pin + n_in; double* ou = ox + B * nx; double* os = ou + B * nu;
-    for (size_t b = 0; b < B; ++b) {
-        pt[b] = t[b * (t_stride ? 1 : 0)];
-        std::memcpy(px + b * nx, x + b * (size_t)h->nxf, sizeof(double) * nx);
-        if (ndyn) { std::memcpy(pd + b * ndyn, x + b * (size_t)h->nxf + nx, sizeof(double) * ndyn); std::memcpy(h->hdyn0.data() + b * ndyn, pd + b * ndyn, sizeof(double) * ndyn); }
-    }
+    instance_times(h->B, t, t_stride, pt);
+    upr_iface_split(d.nx, h->P.n_dyn, x, B, px, ndyn ? pd : nullptr);
+    if (ndyn) std::memcpy(h->hdyn0.data(), pd, sizeof(double) * B * ndyn);
     auto t0c = std::chrono::steady_clock::now();
     // the stream operations of one control period
     auto enqueue = [&]() -> int {
@@ -2023,11 +1999,7 @@ int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x,
     }
     UPR_HIP(hipStreamSynchronize(h->stream));
     h->last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0c).count();
-    for (size_t b = 0; b < B; ++b) {
-        double* o = x_out + b * (size_t)h->nxf;
-        std::memcpy(o, ox + b * nx, sizeof(double) * nx);
-        if (ndyn) std::memcpy(o + nx, pd + b * ndyn, sizeof(double) * ndyn);   // (evaluated at the observation's own time: the obstacle where it was observed)
-    }
+    upr_iface_join(d.nx, h->P.n_dyn, ox, pd, B, x_out);   // (evaluated at the observation's own time: the obstacle where it was observed)
     std::memcpy(u_out, ou, sizeof(double) * B * nu);
     if (stats_out) std::memcpy(stats_out, os, sizeof(double) * B * UPR_NSTATS);
     return 0;
@@ -2041,11 +2013,7 @@ int upr_batch_get_feedback(upr_batch* h, double* K) {
     const upr_dims& d = h->d;
     std::vector<double> Kr((size_t)h->B * d.N * d.nu * d.nx);
     if (get_feedback_core(h, Kr.data())) return 1;
-    const size_t rows = (size_t)h->B * d.N * d.nu;
-    for (size_t r = 0; r < rows; ++r) {   // the obstacle is not fed back: zero columns
-        std::memcpy(K + r * h->nxf, Kr.data() + r * d.nx, sizeof(double) * d.nx);
-        for (int c = d.nx; c < h->nxf; ++c) K[r * h->nxf + c] = 0.0;
-    }
+    upr_iface_join_zero(d.nx, h->P.n_dyn, Kr.data(), (size_t)h->B * d.N * d.nu, K);   // the obstacle is not fed back: zero columns
     return 0;
 }
 
@@ -2055,11 +2023,17 @@ int upr_batch_qp_step(upr_batch* h, double* dxs, double* dus) {
     const upr_dims& d = h->d;
     std::vector<double> xr((size_t)h->B * (d.N + 1) * d.nx);
     if (qp_step_core(h, xr.data(), dus)) return 1;
-    const size_t n = (size_t)h->B * (d.N + 1);
-    for (size_t i = 0; i < n; ++i) {
-        std::memcpy(dxs + i * h->nxf, xr.data() + i * d.nx, sizeof(double) * d.nx);
-        for (int c = d.nx; c < h->nxf; ++c) dxs[i * h->nxf + c] = 0.0;
-    }
+    upr_iface_join_zero(d.nx, h->P.n_dyn, xr.data(), (size_t)h->B * (d.N + 1), dxs);   // the obstacle is data of the QP: its step is zero
+    return 0;
+}
+
+int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double* nu, double* yN, double* lam, int* ni_out) {
+    UPR_ENTER(h);
+    if (!h->P.n_dyn || !dxs) return qp_kkt_core(h, dxs, dus, pi, nu, yN, lam, ni_out);
+    const upr_dims& d = h->d;
+    std::vector<double> xr((size_t)h->B * (d.N + 1) * d.nx);
+    if (qp_kkt_core(h, xr.data(), dus, pi, nu, yN, lam, ni_out)) return 1;
+    upr_iface_join_zero(d.nx, h->P.n_dyn, xr.data(), (size_t)h->B * (d.N + 1), dxs);
     return 0;
 }
 
