@@ -456,8 +456,38 @@ int upr_batch_speed_margin_points(upr_batch* h, int n, const double* x, int n_sc
                                   double* speed, double* z, double* y, int* iters);
 int upr_batch_speed_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double s_max, double* speed,
                                 int* iters, double* window, int* knot, double* limit);
-/* device time (ms) of the kernel launches of the last balance check, friction margin or speed margin on the handle, HIP events around
- * them (copies excluded) */
+/* ------------------------------------------------------------------------------------------------
+ * Path-acceleration margin (upright_amd/csrc/upr_pathacc.h): how hard a state can brake along its own path, or accelerate along it,
+ * with the objects still balanced.  A trajectory replayed with the time scaling s(t) turns a knot x = (q, v, a) into x(s0, d) = (q,
+ * s0 v, s0^2 a + d v), s0 = sdot (`speed`), d = sddot in 1 / s; d < 0 is braking (from sdot = 1, sddot = -beta stops the replay in
+ * 1 / beta seconds if held).  b(d) = b(0) + d b2 and A does not depend on d, so rho^2 is convex in d and the balanced d form one
+ * interval.  d is accepted iff rho(x(s0, d); theta) <= 1e-8 max(|b(d)|, 1) (UPR_BAL_FEAS) on the cold projection of the rho calls,
+ * b(d) rebuilt from the transformed state at every evaluation.
+ *   Evaluations lie on the grid d(k) = d_max (k - 2^31) 2^-31, k = 0 .. 2^32: -d_max, 0 and d_max are grid points.  The algorithm is
+ *   the speed margin's with d = 0 as the nominal point: -d_max and d_max first; both accepted: done.  -d_max accepted: 32 halvings
+ *   for the upper end.  Else a seed: d = 0, else d_max, else a descent search on the slope r' b2 (32 halvings without an accepted
+ *   point: no d is accepted; its first midpoint is d = 0 again); then halvings on both sides of the seed.
+ *       accel[4]  d_lo: the smallest accepted d found (-d_max if -d_max is accepted); d_lo_out: the largest rejected d below it (-inf
+ *                 if none); d_hi: the largest accepted d found (d_max if d_max is accepted); d_hi_out: the smallest rejected d above
+ *                 it (+inf if none).  No d accepted: +inf, -d_max, -inf, d_max.  A bisected end has |in - out| = d_max 2^-31; the
+ *                 reported ends are the accepted side.  0 in [d_lo, d_hi] iff the state is balanced at speed s0; d_hi < 0: it is
+ *                 balanced only while braking at least that hard; d_lo: the hardest balanced braking.
+ *       z[2], y[2], iters   as the speed margin's, at d_lo / d_hi and at d_lo_out / d_hi_out.
+ *   upr_batch_path_accel_margin_points  layouts of upr_batch_speed_margin_points: accel[n][n_scen][4], z[n][n_scen][2][ncol] or NULL,
+ *       y[n][n_scen][2][6 nb] or NULL, iters[n][n_scen] or NULL.  Host pointers.
+ *   upr_batch_path_accel_margin_plan  the knots of the current plan on the device, as upr_batch_speed_margin_plan: accel[B][N+1]
+ *       [n_scen][4] or NULL, iters or NULL; window[B][n_scen][2] or NULL: the largest d_lo and the smallest d_hi over the knots,
+ *       knot[B][n_scen][2] (or NULL) the first knot attaining each; limit[B][2] or NULL: the interval (lo, hi) of d for which
+ *       s0^2 a_i + d v_i stays inside the acceleration box of every joint at every knot ((-inf, +inf) for a plan at rest; lo > hi
+ *       when s0^2 a is outside the box already).  Jerk is not part of it: a step in sddot is an impulse of jerk.  accel and window
+ *       must not both be NULL.
+ *   d_max must be finite and > 0, speed finite and >= 0.  Scratch, timing and the state of the handle as the friction margin above. */
+int upr_batch_path_accel_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point,
+                                       double d_max, double speed, double* accel, double* z, double* y, int* iters);
+int upr_batch_path_accel_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double d_max, double speed,
+                                     double* accel, int* iters, double* window, int* knot, double* limit);
+/* device time (ms) of the kernel launches of the last balance check, friction margin, speed margin or path-acceleration margin on the
+ * handle, HIP events around them (copies excluded) */
 double upr_batch_balance_ms(upr_batch* h);
 
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):

@@ -36,6 +36,7 @@
 #include "upr_balance.h"
 #include "upr_margin.h"
 #include "upr_speed.h"
+#include "upr_pathacc.h"
 #include "upr_iface.h"
 
 namespace {
@@ -826,7 +827,7 @@ int advance_impl(upr_batch* h) {
     return 0;
 }
 
-// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h): the twelve entry points end here, in balance_call.  An entry fills a REQUEST, which
+// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h): the fourteen entry points end here, in balance_call.  An entry fills a REQUEST, which
 // names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
 // go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
 // the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
@@ -835,8 +836,9 @@ int advance_impl(upr_batch* h) {
 // whatever is in flight and the one synchronisation is the last statement.  The scratch of the calls is one block on the handle
 // that serves nothing else and only grows (bal_buf): a call in the steady state allocates and frees nothing.
 enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
-// the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h)
-enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3 };
+// the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h) | the
+// path-acceleration margin (upr_pathacc.h)
+enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4 };
 struct bal_request {
     const char* who = "";     // the entry, as its messages name it
     const char* needs = "";   // ... and what they say about its required pointers
@@ -854,6 +856,9 @@ struct bal_request {
     // the speed margin: out is speed, four doubles per job; z and y hold two certificates per job, the lower end first; worst /
     // worst_knot ([B][n_scen][2]; plan) are the window over the knots and the knots that attain it, limit [B] the limit speed
     double s_max = 0.0; double* limit = nullptr;
+    // the path-acceleration margin: out is accel, four doubles per job, certificates and reductions as the speed margin's; the range
+    // [-d_max, d_max] of sddot at sdot = speed; limit [B][2] the interval of sddot the acceleration boxes allow
+    double d_max = 0.0, speed = 1.0;
     // the answers on the host; all but the required ones may be NULL.  worst / worst_knot ([B][n_scen][n_grp]; plan, per group): the
     // largest kappa_hi over the knots of an instance, reduced on the device; out may then be NULL and kappa_hi stays on the device
     double* out = nullptr;   // rho | kappa_hi
@@ -895,6 +900,8 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
     const bool margin = r.quantity == BAL_MARGIN || r.quantity == BAL_MARGIN_GROUPS;
     if (margin && (!(r.kappa_max > 0) || !std::isfinite(r.kappa_max))) return fail("friction margin: kappa_max must be finite and > 0");
     if (r.quantity == BAL_SPEED && (!(r.s_max > 1) || !std::isfinite(r.s_max))) return fail("speed margin: s_max must be finite and > 1");
+    if (r.quantity == BAL_PATHACC && (!(r.d_max > 0) || !std::isfinite(r.d_max) || !(r.speed >= 0) || !std::isfinite(r.speed)))
+        return fail("path-acceleration margin: d_max must be finite and > 0, speed finite and >= 0");
     if (r.quantity == BAL_MARGIN_GROUPS && balance_check_groups(h, r.n_grp, r.group_mask)) return 1;
     if (!r.plan && r.n <= 0) return 2;
     if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst)) return refuse(r.needs);
@@ -911,19 +918,23 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
 }
 
 // form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
-// group, the speed margin.  Every kernel takes (its record, upr_bal_dims, long long jobs); the record is upr_bal_args, upr_mar_args
-// for the common margin, upr_grp_args for the groups and upr_spd_args for the speed margin.
-const void* const bal_kernels[2][6] = {
+// group, the speed margin, the path-acceleration margin.  Every kernel takes (its record, upr_bal_dims, long long jobs); the record is
+// upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the groups, upr_spd_args for the speed margin and upr_pac_args for
+// the path-acceleration margin.
+const void* const bal_kernels[2][7] = {
     /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
-                    (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel},
+                    (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel,
+                    (const void*)upr_bal_pathacc1_kernel},
     /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
-                    (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel}};
+                    (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel,
+                    (const void*)upr_bal_pathacc_kernel}};
 struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
 
 int balance_launch(upr_batch* h, const bal_request& r) {
     const upr_dims& d = h->d;
     upr_bal_dims L = h->bal.L;
-    const bool wave = h->bal.form == BAL_WAVE, speed = r.quantity == BAL_SPEED, margin = r.quantity != BAL_RHO && !speed, groups = r.quantity == BAL_MARGIN_GROUPS;
+    const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, speed = r.quantity == BAL_SPEED || pathacc;   // (speed: the four-double layout)
+    const bool margin = r.quantity != BAL_RHO && !speed, groups = r.quantity == BAL_MARGIN_GROUPS;
     const long long n = bal_points(h, r), njobs = n * r.n_scen, ng = r.n_grp, nout = njobs * ng;
     const bool want_worst = r.worst || r.worst_knot;
     const long long nworst = want_worst ? (long long)h->B * r.n_scen * (speed ? 2 : ng) : 0;
@@ -951,7 +962,8 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const size_t o_gm = region(sizeof(unsigned) * ng, groups, r.group_mask, nullptr);
     const size_t o_w = region(sizeof(double) * nworst, want_worst, nullptr, r.worst);
     const size_t o_wk = region(sizeof(int) * nworst, want_worst, nullptr, r.worst_knot);
-    const size_t o_lim = region(sizeof(double) * h->B, r.limit != nullptr, nullptr, r.limit);
+    const size_t o_lim = region(sizeof(double) * h->B * (pathacc ? 2 : 1), r.limit != nullptr, nullptr, r.limit);
+    const size_t o_vee = region(sizeof(double) * n * 3, pathacc, nullptr, nullptr);
     if (balance_scratch(h, total)) return 1;
     char* base = (char*)h->bal_buf;
     for (int i = 0; i < nup; ++i) UPR_HIP(hipMemcpyAsync(base + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, h->stream));
@@ -960,7 +972,9 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const double* dx = r.plan ? h->xs : (const double*)(base + o_x);
     double *dst = (double*)(base + o_st), *drho = (double*)(base + o_rho);
     const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
-    if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
+    if (pathacc && h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_vee_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
+    else if (pathacc) hipLaunchKernelGGL(upr_bal_state_vee_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
+    else if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
     else hipLaunchKernelGGL(upr_bal_state_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
     UPR_HIP(hipGetLastError());
     upr_bal_args A;
@@ -975,7 +989,12 @@ int balance_launch(upr_batch* h, const bal_request& r) {
         M.kappa_lo = r.kappa_lo ? (double*)(base + o_lo) : nullptr; M.y = r.y ? (double*)(base + o_y) : nullptr;
     }
     upr_spd_args S;
-    if (speed) { S.J = A; S.J.rho = nullptr; S.s_max = r.s_max; S.speed = drho; S.y = r.y ? (double*)(base + o_y) : nullptr; }
+    if (speed && !pathacc) { S.J = A; S.J.rho = nullptr; S.s_max = r.s_max; S.speed = drho; S.y = r.y ? (double*)(base + o_y) : nullptr; }
+    upr_pac_args C;
+    if (pathacc) {
+        C.J = A; C.J.rho = nullptr; C.d_max = r.d_max; C.speed = r.speed; C.vee = (const double*)(base + o_vee); C.accel = drho;
+        C.y = r.y ? (double*)(base + o_y) : nullptr;
+    }
     upr_grp_args X;
     if (groups) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = r.mu_base ? (const double*)(base + o_mu) : nullptr; }
     // lane form: 64 jobs per workgroup, the groups on the y axis.  Wave form: a workgroup is one wave and the jobs (for the groups:
@@ -983,9 +1002,15 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     // the largest shape share a CU inside the 160 KiB)
     long long count = (wave && groups) ? nout : njobs;
     const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
-    void* args[] = {speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
+    void* args[] = {pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
     UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
-    if (speed && (want_worst || r.limit)) {
+    if (pathacc && (want_worst || r.limit)) {
+        const long long lanes = nworst + (r.limit ? h->B : 0);
+        hipLaunchKernelGGL(upr_bal_pathacc_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
+                           d.N + 1, r.n_scen, nworst, h->B, d.nx, r.speed, (const double*)h->xs, (double*)(base + o_w),
+                           r.worst_knot ? (int*)(base + o_wk) : nullptr, r.limit ? (double*)(base + o_lim) : nullptr);
+        UPR_HIP(hipGetLastError());
+    } else if (speed && (want_worst || r.limit)) {
         const long long lanes = nworst + (r.limit ? h->B : 0);
         hipLaunchKernelGGL(upr_bal_speed_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
                            d.N + 1, r.n_scen, nworst, h->B, d.nx, d.nu, (const double*)h->xs, (const double*)h->us, (double*)(base + o_w),
@@ -1761,6 +1786,22 @@ int upr_batch_speed_margin_plan(upr_batch* h, int n_scen, const double* params, 
     return balance_call(h, {.who = "upr_batch_speed_margin_plan", .needs = "speed and window must not both be NULL", .plan = true, .n_scen = n_scen,
                             .params = params, .per = per_instance != 0, .quantity = BAL_SPEED, .s_max = s_max, .limit = limit, .out = speed, .iters = iters,
                             .worst = window, .worst_knot = knot});
+}
+
+int upr_batch_path_accel_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double d_max, double speed,
+                                       double* accel, double* z, double* y, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_path_accel_margin_points", .needs = "x, params and accel must not be NULL", .n = n, .x = x, .n_scen = n_scen,
+                            .params = params, .per = per_point != 0, .quantity = BAL_PATHACC, .d_max = d_max, .speed = speed, .out = accel, .z = z, .y = y,
+                            .iters = iters});
+}
+
+int upr_batch_path_accel_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double d_max, double speed, double* accel, int* iters,
+                                     double* window, int* knot, double* limit) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_path_accel_margin_plan", .needs = "accel and window must not both be NULL", .plan = true, .n_scen = n_scen,
+                            .params = params, .per = per_instance != 0, .quantity = BAL_PATHACC, .limit = limit, .d_max = d_max, .speed = speed, .out = accel,
+                            .iters = iters, .worst = window, .worst_knot = knot});
 }
 
 double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }

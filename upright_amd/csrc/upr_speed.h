@@ -134,6 +134,24 @@ static UPR_HDI void upr_spd_scale(const double* st, double s, double (&out)[UPR_
     for (int i = 0; i < 9; ++i) out[i] = st[i];
     for (int i = 0; i < 3; ++i) { out[9 + i] = s * st[9 + i]; out[12 + i] = s2 * st[12 + i]; out[15 + i] = s2 * st[15 + i]; }
 }
+// ---- the job of a one-parameter margin on the grid -----------------------------------------------------------------------------------
+// upr_spd_ctl decides on an integer grid and does not know what the grid parametrises.  A POLICY names the places where two
+// quantities on it differ (this one and the path-acceleration margin of upr_pathacc.h) -- the grid point -> parameter map, the record
+// transform and the two records the slope is taken between:
+//   begin(c)                  upr_spd_begin with the nominal point of the quantity;
+//   record(st, pt, k, out)    the record of point pt at grid point k;
+//   slope_ends(st, pt, a, b)  the two records the slope of rho^2 / 2 is taken between, g = r' (b(b) - b(a));
+//   answer(c, out)            the four doubles of the job from the neighbours the decisions ended on.
+struct upr_spd_replay {   // this quantity: the replay speed s(k) = s_max k 2^-32
+    double s_max;
+    UPR_HDI void begin(upr_spd_ctl& c) const { upr_spd_begin(c, s_max); }
+    UPR_HDI void record(const double* st, long long, unsigned long long k, double (&out)[UPR_BAL_ST]) const { upr_spd_scale(st, upr_spd_at(k, s_max), out); }
+    UPR_HDI void slope_ends(const double* st, long long, double (&s0)[UPR_BAL_ST], double (&s1)[UPR_BAL_ST]) const {
+        upr_spd_scale(st, 0.0, s0);
+        upr_spd_scale(st, 1.0, s1);
+    }
+    UPR_HDI void answer(const upr_spd_ctl& c, double* out) const { upr_spd_answer(c, s_max, out); }
+};
 // r' (b1 - b0) of one body: its rows of the right-hand side at s = 1 and at rest through the rhs routine
 static UPR_HDI double upr_spd_slope1(const upr_problem* P, const double* st, const double* bpk, double eq_scale, const double* r) {
     double s0[UPR_BAL_ST], s1[UPR_BAL_ST], b0[6], b1[6];
@@ -145,17 +163,30 @@ static UPR_HDI double upr_spd_slope1(const upr_problem* P, const double* st, con
     for (int c = 0; c < 6; ++c) g += r[c] * (b1[c] - b0[c]);
     return g;
 }
+// ... and between the two ends a policy names
+template <class POL>
+static UPR_HDI double upr_spd_slope1(const POL& pol, const upr_problem* P, const double* st, long long pt, const double* bpk, double eq_scale, const double* r) {
+    double s0[UPR_BAL_ST], s1[UPR_BAL_ST], b0[6], b1[6];
+    pol.slope_ends(st, pt, s0, s1);
+    upr_bal_rhs1(P, s0, bpk, eq_scale, b0);
+    upr_bal_rhs1(P, s1, bpk, eq_scale, b1);
+    double g = 0.0;
+    for (int c = 0; c < 6; ++c) g += r[c] * (b1[c] - b0[c]);
+    return g;
+}
 
 // ---- a wave per job ------------------------------------------------------------------------------------------------------------------
-static UPR_HDI void upr_bal_speed_job(const upr_ctx& ctx, const upr_spd_args& S, const upr_bal_dims& L, long long job, double* W) {
-    const upr_bal_args& A = S.J;
+// A: the jobs; out [n][n_scen][4]; y [n][n_scen][2][6 nb] or NULL
+template <class POL>
+static UPR_HDI void upr_bal_grid_job(const upr_ctx& ctx, const upr_bal_args& A, const POL& pol, double* out, double* y, const upr_bal_dims& L, long long job,
+                                     double* W) {
     const upr_problem* P = A.P;
     const long long pt = job / A.n_scen;
     const int sc = (int)(job - pt * A.n_scen);
     const double* bp = A.params + (size_t)10 * P->nb * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
     const double* st = A.st + (size_t)pt * UPR_BAL_ST;
     double* zo = A.z ? A.z + (size_t)job * 2 * L.ncol : nullptr;
-    double* yo = S.y ? S.y + (size_t)job * 2 * L.m : nullptr;
+    double* yo = y ? y + (size_t)job * 2 * L.m : nullptr;
     double* r = W + L.o_r;
     // the slope's partial sums, one per body, in the s vector of the projection (mp = min(6 nb, ncol) doubles, free once the
     // projection has returned): needs nb <= mp, which holds whenever every body has a contact (ncol >= nc >= nb); a shape with fewer
@@ -165,11 +196,11 @@ static UPR_HDI void upr_bal_speed_job(const upr_ctx& ctx, const upr_spd_args& S,
     if (zo) UPR_FOR(j, L.ncol) { zo[j] = 0.0; zo[L.ncol + j] = 0.0; }
     if (yo) UPR_FOR(e, L.m) { yo[e] = 0.0; yo[L.m + e] = 0.0; }
     upr_spd_ctl c;
-    upr_spd_begin(c, S.s_max);
+    pol.begin(c);
     int total = 0;
     while (c.phase != UPR_SPD_DONE) {
         double ss[UPR_BAL_ST];
-        upr_spd_scale(st, upr_spd_at(c.k, S.s_max), ss);
+        pol.record(st, pt, c.k, ss);
         UPR_WSYNC();   // (the previous evaluation, or the previous job of this wave, is done with the workspace)
         upr_bal_rhs(ctx, P, ss, bp, A.eq_scale, W + L.o_b);
         int np, it; double bnorm;
@@ -180,7 +211,7 @@ static UPR_HDI void upr_bal_speed_job(const upr_ctx& ctx, const upr_spd_args& S,
         if (!ok && c.phase == UPR_SPD_DESCENT) {
             // a body per lane, then every lane adds the bodies in their order (the s vector of the projection is free by now)
             UPR_WSYNC();
-            UPR_FOR(k, P->nb) part[k] = upr_spd_slope1(P, st, bp + 10 * k, A.eq_scale, r + 6 * k);
+            UPR_FOR(k, P->nb) part[k] = upr_spd_slope1(pol, P, st, pt, bp + 10 * k, A.eq_scale, r + 6 * k);
             UPR_WSYNC();
             for (int k = 0; k < P->nb; ++k) g += part[k];
         }
@@ -193,13 +224,59 @@ static UPR_HDI void upr_bal_speed_job(const upr_ctx& ctx, const upr_spd_args& S,
         }
     }
     if (ctx.tid == 0) {
-        upr_spd_answer(c, S.s_max, S.speed + (size_t)job * 4);
+        pol.answer(c, out + (size_t)job * 4);
         if (A.iters) A.iters[job] = total;
     }
+}
+static UPR_HDI void upr_bal_speed_job(const upr_ctx& ctx, const upr_spd_args& S, const upr_bal_dims& L, long long job, double* W) {
+    upr_bal_grid_job(ctx, S.J, upr_spd_replay{S.s_max}, S.speed, S.y, L, job, W);
 }
 
 // ---- one-body arrangements: a lane per job ----------------------------------------------------------------------------------------------
 // one copy of the projection's code for all evaluations, as upr_bal_margin_job1
+template <class POL>
+static UPR_HDI void upr_bal_grid_job1(const upr_bal_args& A, const POL& pol, double* out, double* y, const upr_bal_dims& L, long long job) {
+    const upr_problem* P = A.P;
+    const long long pt = job / A.n_scen;
+    const int sc = (int)(job - pt * A.n_scen);
+    const double* bp = A.params + (size_t)10 * ((A.pdiv ? (pt / A.pdiv) * A.n_scen : 0) + sc);
+    const double* st = A.st + (size_t)pt * UPR_BAL_ST;
+    double* zo = A.z ? A.z + (size_t)job * 2 * L.ncol : nullptr;
+    double* yo = y ? y + (size_t)job * 12 : nullptr;
+    if (zo) for (int j = 0; j < 2 * L.ncol; ++j) zo[j] = 0.0;
+    if (yo) for (int e = 0; e < 12; ++e) yo[e] = 0.0;
+    upr_spd_ctl c;
+    pol.begin(c);
+    int total = 0;
+    while (c.phase != UPR_SPD_DONE) {
+        double ss[UPR_BAL_ST], b[6];
+        pol.record(st, pt, c.k, ss);
+        upr_bal_rhs1(P, ss, bp, A.eq_scale, b);
+        double bb2 = 0.0;
+        for (int e = 0; e < 6; ++e) bb2 += b[e] * b[e];
+        const double bnorm = sqrt(bb2), s1 = bnorm > 1.0 ? bnorm : 1.0;
+        double r[6], zp[UPR_BAL1_MP], pc[UPR_BAL1_MP][6], G[UPR_BAL1_MP][UPR_BAL1_MP];
+        int pidx[UPR_BAL1_MP], np;
+        const int it = upr_bal_project1(P, L, bp, A.eq_scale, upr_bal_mu_one(), b, UPR_BAL_TOL * s1, r, zp, pidx, np, pc, G);
+        total += it;
+        double rr = 0.0;
+        for (int e = 0; e < 6; ++e) rr += r[e] * r[e];
+        const bool ok = sqrt(rr) <= UPR_BAL_FEAS * s1;
+        const double g = (!ok && c.phase == UPR_SPD_DESCENT) ? upr_spd_slope1(pol, P, st, pt, bp, A.eq_scale, r) : 0.0;
+        const unsigned ends = upr_spd_feed(c, ok, g);
+        if (ok) {
+            if (zo) for (int e = 0; e < 2; ++e) if ((ends >> e) & 1u) upr_bal_put_z1(L.ncol, zp, pidx, np, zo + (size_t)e * L.ncol);
+        } else if (yo && ends) {
+            if (it < upr_bal_iter_cap(L.ncol)) upr_bal_polish1(pc, G, np, r);
+            for (int e = 0; e < 2; ++e) if ((ends >> e) & 1u) for (int i = 0; i < 6; ++i) yo[6 * e + i] = r[i];
+        }
+    }
+    pol.answer(c, out + (size_t)job * 4);
+    if (A.iters) A.iters[job] = total;
+}
+// The lane form of the speed margin keeps a body of its own: routed through upr_bal_grid_job1 the compiler schedules the 256-VGPR
+// kernel differently (equal size, other register assignment), and the speed kernels' code is to stay what it was.  The two differ in
+// the three places the policy names and nowhere else.
 static UPR_HDI void upr_bal_speed_job1(const upr_spd_args& S, const upr_bal_dims& L, long long job) {
     const upr_bal_args& A = S.J;
     const upr_problem* P = A.P;

@@ -518,8 +518,55 @@ class BatchMPC:
             return w, knot, limit
         return self._asked_for(speed[..., 0::2].copy(), speed[..., 1::2].copy() if want_out else None, iters)
 
+    def path_accel_margin(self, x, params, d_max=8.0, speed=1.0, want_out=False, want_z=False, want_y=False, want_iters=False):
+        """d (n, n_scen, 2) = (d_lo, d_hi): the interval of path accelerations sddot (1 / s) at which the robot states x (n, 3 nq) are
+        balanced under the inertial parameters params (layouts of balance_check; upr_batch_path_accel_margin_points).  Replaying a
+        trajectory with the time scaling s(t), sdot = speed and sddot = d, turns a knot (q, v, a) into (q, speed v, speed^2 a + d v);
+        d counts as balanced when the distance rho there is <= 1e-8 max(|b|, 1), the rule of friction_margin.  d < 0 is braking
+        along the path (the geometric path is kept): d_lo is the hardest balanced braking (-d_max: balanced down to -d_max; the
+        default 8 stops a replay at speed 1 within 125 ms), d_hi the hardest balanced acceleration; d_lo <= 0 <= d_hi iff the state
+        itself is balanced at this speed; d_hi < 0: it is balanced only while braking at least that hard; (inf, -inf): no d in
+        [-d_max, d_max] balances it.  Both ends are the accepted, conservative side of a bracket of width d_max 2^-31.  d_max must
+        be finite and > 0, speed finite and >= 0.
+
+        Returns d alone or the tuple (d, out, z, y, iters) restricted to what was asked for: out (n, n_scen, 2) = (d_lo_out,
+        d_hi_out) the rejected neighbours of the two ends (-inf below a d_lo of -d_max, inf above a d_hi of d_max; (-d_max, d_max)
+        where no d is accepted); z (n, n_scen, 2, ncol) >= 0 the generator multipliers at d_lo and at d_hi; y (n, n_scen, 2, 6 nb)
+        the residuals at d_lo_out and d_hi_out, separating directions; iters (n, n_scen) the least-squares solves over all
+        evaluations (at most 3 + 3 * 32 of them)."""
+        x, n, params, n_scen, per_point = self._points_args(x, params)
+        acc, z, y, iters = self._outputs((n, n_scen), (True, (4,), F8), (want_z, (2, self.balance_columns), F8), (want_y, (2, self.ne), F8),
+                                         (want_iters, (), I4))
+        check(self._lib.upr_batch_path_accel_margin_points(self._h, n, ptr(x), n_scen, ptr(params), per_point, float(d_max), float(speed), ptr(acc),
+                                                           ptr(z), ptr(y), iptr(iters)))
+        return self._asked_for(acc[..., 0::2].copy(), acc[..., 1::2].copy() if want_out else None, z, y, iters)
+
+    def path_accel_margin_plan(self, params=None, d_max=8.0, speed=1.0, want_out=False, want_iters=False, window=False):
+        """d (B, N + 1, n_scen, 2) = (d_lo, d_hi) at the knots of the current plan, evaluated where they lie on the device
+        (upr_batch_path_accel_margin_plan); params as in balance_check_plan, the quantity as in path_accel_margin.  With want_out /
+        want_iters the tuple (d, out, iters) restricted to what was asked for.
+
+        window=True: instead of d per knot the triple (window (B, n_scen, 2), knot (B, n_scen, 2), limit (B, 2)) -- the largest d_lo
+        and the smallest d_hi over the knots of every instance (the sddot at which the WHOLE plan stays balanced in a scenario if all
+        knots brake alike), the first knot that attains each, and the interval (lo, hi) of d for which speed^2 a + d v of every knot
+        stays inside the acceleration bounds of the problem ((-inf, inf) for a plan at rest, lo > hi if speed^2 a is outside them
+        already; jerk is not part of it: a step in sddot is an impulse of jerk); reduced on the device, only these are downloaded.
+        want_out / want_iters are not available with it."""
+        n_scen, per_instance, params = self._plan_params(params)
+        if window and (want_out or want_iters):
+            raise ValueError("window=True returns the reductions alone")
+        acc, iters = self._outputs((self.B, self.N + 1, n_scen), (not window, (4,), F8), (want_iters, (), I4))
+        w, knot = self._outputs((self.B, n_scen, 2), (window, (), F8), (window, (), I4))
+        limit = np.zeros((self.B, 2)) if window else None
+        check(self._lib.upr_batch_path_accel_margin_plan(self._h, n_scen, ptr(params), per_instance, float(d_max), float(speed), ptr(acc), iptr(iters),
+                                                         ptr(w), iptr(knot), ptr(limit)))
+        if window:
+            return w, knot, limit
+        return self._asked_for(acc[..., 0::2].copy(), acc[..., 1::2].copy() if want_out else None, iters)
+
     def balance_ms(self):
-        """Device time (ms) of the kernel launches of the last balance check, friction margin or speed margin (HIP events around them)."""
+        """Device time (ms) of the kernel launches of the last balance check, friction margin, speed margin or path-acceleration margin
+        (HIP events around them)."""
         return float(self._lib.upr_batch_balance_ms(self._h))
 
     def balance_forces(self, z):
