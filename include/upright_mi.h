@@ -213,14 +213,17 @@ int upr_batch_evaluate(upr_batch* h, const double* t, int t_stride, double* x_ou
  * controller_python_interface.h:46-55):
  *     u(t, x) = (1 - a) [u_j + K_j (x - x_j)] + a [u_j+1 + K_j+1 (x - x_j+1)],   t = t_j + a dt
  * K_j are the Riccati gains of the last QP (sign convention of ocs2: u = bias + K x).  x_obs[B][nx], outputs as
- * upr_batch_evaluate.  Needs use_feedback_policy != 0 at creation. */
+ * upr_batch_evaluate.  Needs use_feedback_policy != 0 at creation.
+ * The gains are formed on demand: an advance leaves them in the factors of its last QP, and this call forms the one or two knots
+ * it interpolates between from there, per instance, in the evaluating kernel -- no array of all gains is written for it. */
 int upr_batch_evaluate_policy(upr_batch* h, const double* t, int t_stride, const double* x_obs, double* x_out, double* u_out);
 /* One control period of the reference's loop in ONE call and one synchronisation: what ControllerManager.step does with three
  * (manager.py:156-176: setObservation(t, x) -> advanceMpc() -> evaluateMpcSolution(t, x, x_opt, u_opt)), for callers that replan
  * every period.  The observation is uploaded once (the policy is evaluated at the state that was just observed, at its own time),
  * transfers go through the engine's pinned staging buffer, and the statistics of the solve come back with the result.
  * x[B][nx_full] observed states, x_out[B][nx_full], u_out[B][nu] as upr_batch_evaluate[_policy]; stats_out[B][UPR_NSTATS] or NULL.
- * Results are bit-identical to the three calls.
+ * Results are bit-identical to the three calls.  The policy reads knot 0 of the plan just solved straight from the QP's factors
+ * (upr_batch_evaluate_policy): a period forms the gains of that one knot and writes no gain array.
  * From the third period in a row that enqueues the same operations (warm start, same SQP iteration count, no event timing ...)
  * the period's stream operations -- copies in, prepare, linearise, QP, line search, policy, copies out -- are replayed as ONE HIP
  * graph launch (UPR_TICK_GRAPH=0: never); upr_batch_tick_graph_replays counts the periods served that way. */
@@ -229,7 +232,12 @@ long long upr_batch_tick_graph_replays(upr_batch* h);
 
 /* ControllerInterface.getLinearFeedbackGain (pybindings.cpp:382-384) at the knots: K[B][N][nu][nx]; jerk rows from the
  * Riccati recursion, contact-force rows from the elimination of the object-dynamics equality
- * (f = f* - Hff^-1 Df' S^-1 C dx). */
+ * (f = f* - Hff^-1 Df' S^-1 C dx).
+ * The whole array is formed at the first call after an advance (one gather kernel over the QP's factors; the device array,
+ * B N nu nx doubles, is allocated at the first call on the handle); further calls until the next advance only copy.  Calls that
+ * solve another QP on the handle (upr_batch_qp_kkt, upr_batch_qp_step, upr_batch_value_function_update) gather it first, so the
+ * gains stay those of the last advance.  UPR_FB_FUSED=1 | 0 at creation: the array with every advance instead, written by the QP
+ * kernel's exit | by the gather kernel behind it. */
 int upr_batch_get_feedback(upr_batch* h, double* K);
 
 /* activation flag of the projectile constraint per instance: the 8th entry of the target state

@@ -74,7 +74,8 @@ class ControllerInterface {
         check(upr_batch_get_solution(h_, s.ts.data(), s.xs.data(), s.us.data()));
         return s;
     }
-    // gains K[B][N][nu][nx] of the linear policy (LinearController::gainArray_)
+    // gains K[B][N][nu][nx] of the linear policy (LinearController::gainArray_): gathered from the last QP's factors at the first
+    // call after an advance (evaluate_policy and tick form only the knots they need and never write this array)
     std::vector<double> feedback_gains() {
         std::vector<double> K((size_t)B_ * P_.N * nu_ * nx_);
         check(upr_batch_get_feedback(h_, K.data()));

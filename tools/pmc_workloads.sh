@@ -4,6 +4,7 @@
 # (FETCH_SIZE | WRITE_SIZE | instruction mix + matrix-pipe busy cycles; --kernel-trace only next to --pmc), condensed into
 # gpurun_out/<tag>_pmc_workloads.csv: workload, kernel, counter, dispatches, per-dispatch mean, batch.  bench.py reads the newest
 # profiles/r*_pmc_workloads.csv (pmc_workload) for `traffic`, `frac_issued` and roofline_linearize.mfma_util of every workload.
+# A pass that fails or overruns its limit ends the script: nothing more is started on the GPU behind it.
 set -u
 TAG=${1:-r04}
 export TMPDIR=/tmp
@@ -12,9 +13,9 @@ mkdir -p $OUT
 MIX="SQ_INSTS_VALU_MFMA_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU"
 for W in headline config3 config4 config5 config5s contract headline_r03; do
   if [ $W = headline ]; then ARGS="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra"; else ARGS="bench.py --only $W --extra-steps 2 --closed-loop-ticks 20 --no-cpu-baseline"; fi
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pw_${TAG}_${W}_fetch -o $W -- python3 $ARGS > $OUT/pw_${TAG}_${W}_fetch.log 2>&1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pw_${TAG}_${W}_write -o $W -- python3 $ARGS > $OUT/pw_${TAG}_${W}_write.log 2>&1
-  rocprofv3 --kernel-trace --pmc $MIX --output-format csv -d $OUT/pw_${TAG}_${W}_mix -o $W -- python3 $ARGS > $OUT/pw_${TAG}_${W}_mix.log 2>&1
+  timeout -k 10 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pw_${TAG}_${W}_fetch -o $W -- python3 $ARGS > $OUT/pw_${TAG}_${W}_fetch.log 2>&1 || exit 1
+  timeout -k 10 240 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pw_${TAG}_${W}_write -o $W -- python3 $ARGS > $OUT/pw_${TAG}_${W}_write.log 2>&1 || exit 1
+  timeout -k 10 240 rocprofv3 --kernel-trace --pmc $MIX --output-format csv -d $OUT/pw_${TAG}_${W}_mix -o $W -- python3 $ARGS > $OUT/pw_${TAG}_${W}_mix.log 2>&1 || exit 1
 done
 python3 - <<PY
 import csv, glob, collections

@@ -31,6 +31,7 @@
 #include "upr_qp3_list.h"
 #include "upr_qp3_launch.h"
 #include "upr_qp_select.h"
+#include "upr_fb_state.h"
 #include "upr_launch_select.h"
 #include "upr_value.h"
 #include "upr_balance.h"
@@ -153,11 +154,48 @@ struct upr_fb_src {
 // Jerk rows: -Hjj^-1 Hux from the Riccati recursion; contact-force rows: -Hff^-1 Df' S^-1 C (the forces
 // follow the state through the object-dynamics equality).
 // NEM / NFM: compile-time bounds of ne / nfc (the per-thread scratch vectors stay in registers for the small shapes)
+// The two pieces every reader of the factors shares (the gather of the whole array and the policy that forms one or two knots):
+// entry (j, c) of knot k's jerk rows, before the sign ...
+__device__ inline double fb_jerk_entry(const upr_dims& d, const upr_fb_src& src, const double* w, int k, int j, int c) {
+    const int nq = d.nq, nx = d.nx;
+    if (src.kind == 3) return w[src.k_base + (long)k * src.k_stride + j * nx + c];
+    const double* V = w + src.k_base + (long)k * src.k_stride;
+    const double* Lji = w + src.lji_base + (long)k * src.lji_stride;
+    double v = 0.0;
+    for (int m = j; m < nq; ++m) v += Lji[m * nq + j] * V[m * nx + c];
+    return v;
+}
+// ... and column c of knot k's contact-force rows, through L_s^-1, D_f', L_f^-1, into out[nu][nx] (the knot's block)
+template <int NEM, int NFM>
+__device__ inline void fb_force_column(const upr_dims& d, const upr_fb_src& src, const double* w, const double* Ck, const double* Dfb, int k, int c, double* out) {
+    const int nq = d.nq, nx = d.nx, ne = d.ne, nfc = d.nfc, nf = d.nf;
+    const double* Lsi = w + src.lsi_base + (long)k * src.lsi_stride;
+    const double* Lfi = w + src.lfi_base + (long)k * src.lfi_stride;
+    double t1[NEM], t2[NEM], t3[NFM];
+    // S^-1 C = Lsi' (Lsi C), block by block (a dense factor is one block of ne rows)
+    const int sb = src.lsi_sb;
+    for (int r = 0; r < ne; ++r) { const int b0 = (r / sb) * sb; const double* Lb = Lsi + (b0 / sb) * sb * sb; double v = 0.0; for (int m = b0; m <= r; ++m) v += Lb[(r - b0) * sb + (m - b0)] * Ck[m * nx + c]; t1[r] = v; }
+    for (int r = 0; r < ne; ++r) { const int b0 = (r / sb) * sb; const double* Lb = Lsi + (b0 / sb) * sb * sb; double v = 0.0; for (int m = r; m < b0 + sb; ++m) v += Lb[(m - b0) * sb + (r - b0)] * t1[m]; t2[r] = v; }
+    for (int i = 0; i < nfc; ++i) { double v = 0.0; for (int r = 0; r < ne; ++r) v += Dfb[r * nfc + i] * t2[r]; t3[i] = v; }
+    for (int ci = 0; ci < d.nc; ++ci) {
+        if (nf == 3) {
+            const double* Bk = Lfi + 9 * ci; const double* x3 = t3 + 3 * ci;
+            double y[3], z[3];
+            for (int a = 0; a < 3; ++a) { double v = 0.0; for (int b2 = 0; b2 <= a; ++b2) v += Bk[3 * a + b2] * x3[b2]; y[a] = v; }
+            for (int a = 0; a < 3; ++a) { double v = 0.0; for (int b2 = a; b2 < 3; ++b2) v += Bk[3 * b2 + a] * y[b2]; z[a] = v; }
+            for (int a = 0; a < 3; ++a) out[(size_t)(nq + 3 * ci + a) * nx + c] = -z[a];
+        } else {
+            const double lf = Lfi[ci];
+            out[(size_t)(nq + ci) * nx + c] = -lf * lf * t3[ci];
+        }
+    }
+}
+
 template <int NEM, int NFM>
 __global__ void feedback_kernel(const upr_problem* P, upr_dims d, upr_fb_src src, const double* ws, const double* lin,
                                 const double* Df, const double* stats, double* fb) {
     const int b = blockIdx.x;
-    const int N = d.N, nq = d.nq, nx = d.nx, nu = d.nu, ne = d.ne, nfc = d.nfc, nf = d.nf;
+    const int N = d.N, nq = d.nq, nx = d.nx, nu = d.nu, ne = d.ne, nfc = d.nfc;
     const double* w = ws + (size_t)b * d.ws_stride;
     double* out = fb + (size_t)b * N * nu * nx;
     if (stats[(size_t)b * UPR_NSTATS + 2] == 2.0) {
@@ -168,40 +206,13 @@ __global__ void feedback_kernel(const upr_problem* P, upr_dims d, upr_fb_src src
     }
     for (int e = threadIdx.x; e < N * nq * nx; e += blockDim.x) {
         const int k = e / (nq * nx), j = (e % (nq * nx)) / nx, c = e % nx;
-        double v;
-        if (src.kind == 3) v = w[src.k_base + (long)k * src.k_stride + j * nx + c];
-        else {
-            const double* V = w + src.k_base + (long)k * src.k_stride;
-            const double* Lji = w + src.lji_base + (long)k * src.lji_stride;
-            v = 0.0;
-            for (int m = j; m < nq; ++m) v += Lji[m * nq + j] * V[m * nx + c];
-        }
-        out[((size_t)k * nu + j) * nx + c] = -v;
+        out[((size_t)k * nu + j) * nx + c] = -fb_jerk_entry(d, src, w, k, j, c);
     }
     const double* Dfb = Df + (size_t)b * ne * nfc;
     for (int e = threadIdx.x; e < N * nx; e += blockDim.x) {
         const int k = e / nx, c = e % nx;
         const double* Ck = lin + ((size_t)b * (N + 1) + k) * d.lin_stride + d.lin_gx;
-        const double* Lsi = w + src.lsi_base + (long)k * src.lsi_stride;
-        const double* Lfi = w + src.lfi_base + (long)k * src.lfi_stride;
-        double t1[NEM], t2[NEM], t3[NFM];
-        // S^-1 C = Lsi' (Lsi C), block by block (a dense factor is one block of ne rows)
-        const int sb = src.lsi_sb;
-        for (int r = 0; r < ne; ++r) { const int b0 = (r / sb) * sb; const double* Lb = Lsi + (b0 / sb) * sb * sb; double v = 0.0; for (int m = b0; m <= r; ++m) v += Lb[(r - b0) * sb + (m - b0)] * Ck[m * nx + c]; t1[r] = v; }
-        for (int r = 0; r < ne; ++r) { const int b0 = (r / sb) * sb; const double* Lb = Lsi + (b0 / sb) * sb * sb; double v = 0.0; for (int m = r; m < b0 + sb; ++m) v += Lb[(m - b0) * sb + (r - b0)] * t1[m]; t2[r] = v; }
-        for (int i = 0; i < nfc; ++i) { double v = 0.0; for (int r = 0; r < ne; ++r) v += Dfb[r * nfc + i] * t2[r]; t3[i] = v; }
-        for (int ci = 0; ci < d.nc; ++ci) {
-            if (nf == 3) {
-                const double* Bk = Lfi + 9 * ci; const double* x3 = t3 + 3 * ci;
-                double y[3], z[3];
-                for (int a = 0; a < 3; ++a) { double v = 0.0; for (int b2 = 0; b2 <= a; ++b2) v += Bk[3 * a + b2] * x3[b2]; y[a] = v; }
-                for (int a = 0; a < 3; ++a) { double v = 0.0; for (int b2 = a; b2 < 3; ++b2) v += Bk[3 * b2 + a] * y[b2]; z[a] = v; }
-                for (int a = 0; a < 3; ++a) out[((size_t)k * nu + nq + 3 * ci + a) * nx + c] = -z[a];
-            } else {
-                const double lf = Lfi[ci];
-                out[((size_t)k * nu + nq + ci) * nx + c] = -lf * lf * t3[ci];
-            }
-        }
+        fb_force_column<NEM, NFM>(d, src, w, Ck, Dfb, k, c, out + (size_t)k * nu * nx);
     }
 }
 
@@ -234,6 +245,59 @@ __global__ void evaluate_policy_kernel(const upr_problem* P, upr_dims d, int B, 
         u_out[(size_t)b * nu + i] = v;
     }
 }
+
+// The same policy while the gains are still in the factors of the advance's last QP (upr_fb_state.h): the workgroup forms the gains
+// of knot j -- and of knot j + 1 where the time lies inside an interval -- into LDS as [nu][nx] with the gather's own formulas
+// (fb_jerk_entry, fb_force_column: one lane per column of the force rows), then lanes i < nu run the dot products of
+// evaluate_policy_kernel in its order.  Per knot it reads K_k, C_k, the two factors and D_f, about what the knot's block of the
+// array holds, and writes nothing but the answer.  Dynamic LDS: 2 nu nx doubles (at most 2 x 108 x 36: under the 64 KiB a kernel
+// gets without asking).  A QP that ended with status 2 has no policy: its instance gets the plan's input.
+template <int NEM, int NFM>
+__global__ void evaluate_policy_factors_kernel(const upr_problem* P, upr_dims d, int B, const double* tsol, const double* xs,
+                                               const double* us, upr_fb_src src, const double* ws, const double* lin, const double* Df,
+                                               const double* stats, const double* t, const double* x_obs, double* x_out, double* u_out) {
+    extern __shared__ double fb_lds[];
+    const int b = blockIdx.x;
+    const int N = d.N, nq = d.nq, nx = d.nx, nu = d.nu, ne = d.ne, nfc = d.nfc;
+    const double* X = xs + (size_t)b * (N + 1) * nx; const double* U = us + (size_t)b * N * nu;
+    const double* xo = x_obs + (size_t)b * nx;
+    double s = (t[b] - tsol[b]) / P->dt;
+    if (s < 0.0) s = 0.0;
+    for (int i = threadIdx.x; i < nx; i += blockDim.x)
+        upr_interp(d, P->dt, tsol[b], X, U, t[b], i, 0, x_out + (size_t)b * nx + i, nullptr);
+    // (s, j, j1 and a are the same in every lane of the workgroup: the branches below are uniform)
+    int j = (int)s; if (j > N - 1) j = N - 1;
+    const double a = (s >= N - 1) ? 0.0 : s - j;
+    const int j1 = (j + 1 < N) ? j + 1 : N - 1;
+    const bool inside = s <= N, policy = stats[(size_t)b * UPR_NSTATS + 2] != 2.0;
+    if (inside && policy) {
+        const double* w = ws + (size_t)b * d.ws_stride;
+        const double* Dfb = Df + (size_t)b * ne * nfc;
+        const int nk = a > 0.0 ? 2 : 1;
+        for (int q = 0; q < nk; ++q) {
+            const int k = q ? j1 : j;
+            double* G = fb_lds + (size_t)q * nu * nx;
+            for (int e = threadIdx.x; e < nq * nx; e += blockDim.x) G[e] = -fb_jerk_entry(d, src, w, k, e / nx, e % nx);
+            const double* Ck = lin + ((size_t)b * (N + 1) + k) * d.lin_stride + d.lin_gx;
+            for (int c = threadIdx.x; c < nx; c += blockDim.x) fb_force_column<NEM, NFM>(d, src, w, Ck, Dfb, k, c, G);
+        }
+    }
+    __syncthreads();
+    const double* K0 = fb_lds; const double* K1 = fb_lds + (size_t)nu * nx;
+    for (int i = threadIdx.x; i < nu; i += blockDim.x) {
+        double v = 0.0;
+        if (inside) {
+            double v0 = U[j * nu + i], v1 = U[j1 * nu + i];
+            if (policy) for (int c = 0; c < nx; ++c) {
+                v0 += K0[(size_t)i * nx + c] * (xo[c] - X[j * nx + c]);
+                if (a > 0.0) v1 += K1[(size_t)i * nx + c] * (xo[c] - X[j1 * nx + c]);
+            }
+            v = (1.0 - a) * v0 + a * v1;
+        }
+        u_out[(size_t)b * nu + i] = v;
+    }
+}
+static_assert(2 * UPR_MAX_NU * UPR_MAX_NX * sizeof(double) <= 64 * 1024, "two knots of gains in the LDS a kernel gets without asking");
 
 }  // namespace
 
@@ -303,7 +367,11 @@ struct upr_batch {
     double* prof = nullptr;
     double *ev_t = nullptr, *ev_xo = nullptr, *ev_x = nullptr, *ev_u = nullptr;   // scratch of the evaluate / evaluate_policy calls
     double* kkt = nullptr;   // multiplier export of the register-resident QP kernel (upr_batch_qp_kkt), allocated on first use
-    double *fb = nullptr, *xs_lin = nullptr;   // feedback gains of the last solve
+    // feedback gains (sqp.use_feedback_policy, fb_on): where those of the last advance are (upr_fb_state.h) and the array
+    // fb[B][N][nu][nx] they are gathered into -- allocated at create where UPR_FB_FUSED is set, at the first gather otherwise
+    bool fb_on = false;
+    upr_fb_track fbt;
+    double *fb = nullptr, *xs_lin = nullptr;
     // dynamic obstacle (n_dyn == 1): observed state per instance (device + host copies, and the one the stored
     // solution belongs to), activation flag of the projectile rows
     double *dyn0 = nullptr, *pflag = nullptr;
@@ -765,9 +833,54 @@ hipError_t vf_raise_lds_limit() { return hipFuncSetAttribute((const void*)upr_va
 // neighbouring problem in closed loop), so the launch hands the instances out sorted by it, longest first (LPT rule):
 // the short ones fill the gaps at the end.  The rank of an instance (ties by index) is computed by its own workgroup of the
 // line-search launch that follows the QP (upr_linesearch.h, order_out): it only permutes which workgroup solves which instance.
+// the gains' array from their sources, as the last QP launch on the handle left them (the gather kernel; no synchronisation)
+int fb_gather(upr_batch* h) {
+    const upr_dims& d = h->d;
+    if (!h->fb && dev_alloc(&h->fb, (size_t)h->B * d.N * d.nu * d.nx)) return 1;
+    if (h->qp.fb.kind == 0) return fail("feedback gains: the selected QP kernel names no source for them");
+    if (d.ne <= 6 && d.nfc <= 12) hipLaunchKernelGGL((feedback_kernel<6, 12>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->qp.fb, h->ws, h->lin, h->Df, h->stats, h->fb);
+    else hipLaunchKernelGGL((feedback_kernel<6 * UPR_MAX_BODIES, 3 * UPR_MAX_CONTACTS>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->qp.fb, h->ws, h->lin, h->Df, h->stats, h->fb);
+    UPR_HIP(hipGetLastError());
+    return 0;
+}
+// before a call overwrites a source of gains that are still in the factors -- the workspace, the records or the statistics of the
+// advance's last QP -- and before the whole array is handed out: gather it (upr_fb_state.h).  The sites: get_feedback_core (the
+// request), kkt_launch and qp_step_core (a linearisation and a QP launch on the handle's own buffers, outside an advance),
+// upr_batch_hold_stats putting statistics back, an advance that runs no QP (it clears the statistics)
+int fb_keep(upr_batch* h) {
+    if (!h->fb_on || !upr_fb_must_gather(h->fbt)) return 0;
+    if (fb_gather(h)) return 1;
+    h->fbt.state = upr_fb_after_gather(h->fbt);
+    return 0;
+}
+// the policy of the stored solution at the times t and the states x_obs (both on the device), by the kernel that reads the gains
+// where they are
+int launch_policy(upr_batch* h, const double* t, const double* x_obs) {
+    const upr_dims& d = h->d;
+    if (upr_fb_policy_from_factors(h->fbt.state)) {
+        if (h->qp.fb.kind == 0) return fail("feedback gains: the selected QP kernel names no source for them");
+        const size_t lds = sizeof(double) * 2 * d.nu * d.nx;
+        if (d.ne <= 6 && d.nfc <= 12) hipLaunchKernelGGL((evaluate_policy_factors_kernel<6, 12>), dim3(h->B), dim3(64), lds, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->qp.fb, h->ws, h->lin, h->Df, h->stats, t, x_obs, h->ev_x, h->ev_u);
+        else hipLaunchKernelGGL((evaluate_policy_factors_kernel<6 * UPR_MAX_BODIES, 3 * UPR_MAX_CONTACTS>), dim3(h->B), dim3(64), lds, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->qp.fb, h->ws, h->lin, h->Df, h->stats, t, x_obs, h->ev_x, h->ev_u);
+    } else {
+        // (no solve yet: the array of zeros, the plan's input)
+        if (!h->fb && dev_alloc(&h->fb, (size_t)h->B * d.N * d.nu * d.nx)) return 1;
+        hipLaunchKernelGGL(evaluate_policy_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->fb, t, x_obs, h->ev_x, h->ev_u);
+    }
+    UPR_HIP(hipGetLastError());
+    return 0;
+}
+
 int advance_impl(upr_batch* h) {
     const upr_dims& d = h->d;
     if (h->vf_state) h->vf_state = 2;
+    const int sqp_iters = h->sqp_iters_next > 0 ? h->sqp_iters_next : h->P.sqp_iters;
+    h->sqp_iters_next = 0;
+    upr_fb_advance fba;
+    if (h->fb_on) {
+        fba = upr_fb_on_advance(h->fbt, sqp_iters, h->qp.fb_fused);
+        if (fba.gather_before && fb_keep(h)) return 1;
+    }
     if (!h->guess_set) {
         hipLaunchKernelGGL(prepare_kernel, dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->B, h->has_prev ? 1 : 0, h->tprev,
                            h->xs_prev, h->us_prev, h->t0, h->x0, h->xs, h->us, h->stats, h->done);
@@ -777,14 +890,12 @@ int advance_impl(upr_batch* h) {
         UPR_HIP(hipMemsetAsync(h->done, 0, sizeof(int) * h->B, h->stream));
         h->guess_set = false;
     }
-    const int sqp_iters = h->sqp_iters_next > 0 ? h->sqp_iters_next : h->P.sqp_iters;
-    h->sqp_iters_next = 0;
     for (int it = 0; it < sqp_iters; ++it) {
         { KernelTimer T(h, 0); if (launch_linearize(h, traj_lin_args(h))) return 1; T.stop(); }
         {
             upr_qp_args Q = make_qp_args(h);
             // the production kernel writes the feedback gains of the advance's LAST QP itself (no gather kernel afterwards)
-            if (h->fb && h->qp.fb_fused && it == sqp_iters - 1) Q.fb = h->fb;
+            if (fba.kernel_writes && it == sqp_iters - 1) Q.fb = h->fb;
             if (h->order_on && h->order_valid) Q.order = h->order;
             // tracked value function: the advance's LAST QP exports its multipliers (exit-only code of the kernel, behind its step)
             if (h->vf_track && it == sqp_iters - 1 && h->qp.exported) { Q.kkt = h->kkt; Q.kkt_stride = h->qp.stride; }
@@ -810,12 +921,8 @@ int advance_impl(upr_batch* h) {
         { KernelTimer T(h, 2); if (launch_linesearch(h, L)) return 1; T.stop(); }
         if (h->order_on) h->order_valid = true;
     }
-    if (h->fb && !(h->qp.fb_fused && sqp_iters > 0)) {   // sqp.use_feedback_policy: gains of the last QP, before anything overwrites its factors
-        if (h->qp.fb.kind == 0) return fail("feedback gains: the selected QP kernel names no source for them");
-        if (d.ne <= 6 && d.nfc <= 12) hipLaunchKernelGGL((feedback_kernel<6, 12>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->qp.fb, h->ws, h->lin, h->Df, h->stats, h->fb);
-        else hipLaunchKernelGGL((feedback_kernel<6 * UPR_MAX_BODIES, 3 * UPR_MAX_CONTACTS>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->qp.fb, h->ws, h->lin, h->Df, h->stats, h->fb);
-        UPR_HIP(hipGetLastError());
-    }
+    if (fba.gather_after && fb_gather(h)) return 1;   // UPR_FB_FUSED set: the gains of the last QP with every advance
+    if (h->fb_on) h->fbt.state = fba.state;
     h->hdyn_prev = h->hdyn0;
     // remember the solution for the next warm start / policy evaluation (the last line search did, unless there was none)
     if (sqp_iters <= 0) {
@@ -1137,7 +1244,8 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
         if (const char* e = getenv("UPR_QP_NT")) { k.qp_nt_set = true; k.qp_nt = atoi(e); }
         if (const char* e = getenv("UPR_QP_GENERIC_NT")) { k.generic_nt_set = true; k.generic_nt = atoi(e); }
         if (const char* e = getenv("UPR_JIT_NT")) k.jit_nt = atoi(e);
-        if (const char* e = getenv("UPR_FB_FUSED")) k.fb_fused = atoi(e) != 0;
+        if (const char* e = getenv("UPR_FB_FUSED")) { k.fb_fused = atoi(e) != 0; h->fbt.mode = UPR_FB_EAGER; }
+        h->fb_on = P->use_feedback_policy != 0;
         upr_qp_sel& s = h->qp;
         static_cast<upr_qp_choice&>(s) = upr_qp_plan(*P, d, k);
         if (s.source == UPR_QP_FROM_RUN_TIME && s.structure == UPR_QP_STRUCT_PRODUCTION && jit_get(s.cfg, s.nt, &s.jit) != 0) {
@@ -1181,7 +1289,7 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
         dev_alloc(&h->xs_prev, (size_t)B * n1 * d.nx) || dev_alloc(&h->us_prev, (size_t)B * d.N * d.nu) || dev_alloc(&h->tprev, B) ||
         dev_alloc(&h->lin, (size_t)B * n1 * d.lin_stride) || dev_alloc(&h->Df, (size_t)B * d.ne * d.nfc) ||
         dev_alloc(&h->ws, (size_t)B * d.ws_stride) || dev_alloc(&h->stats, (size_t)B * UPR_NSTATS) || dev_alloc(&h->done, B) || dev_alloc(&h->order, B) || dev_alloc(&h->iter_key, ((size_t)B + 3) & ~(size_t)3) ||
-        (P->use_feedback_policy && dev_alloc(&h->fb, (size_t)B * d.N * d.nu * d.nx)) ||
+        (h->fb_on && h->fbt.mode == UPR_FB_EAGER && dev_alloc(&h->fb, (size_t)B * d.N * d.nu * d.nx)) ||
         (P->n_dyn && dev_alloc(&h->pflag, B)))
         return bad();
     h->x0 = h->t0 + (((size_t)B + 1) & ~(size_t)1);   // (the states stay 16-byte aligned)
@@ -1317,7 +1425,7 @@ static int get_solution_core(upr_batch* h, double* ts, double* xs, double* us) {
 
 // the plan at the times t: evaluate, or (policy) evaluate_policy at the observed robot states x_obs[B][nx]
 static int evaluate_core(upr_batch* h, const double* t, int t_stride, bool policy, const double* x_obs, double* x_out, double* u_out) {
-    if (policy && !h->fb) return fail("upr_batch_evaluate_policy: the batch was created with use_feedback_policy = 0");
+    if (policy && !h->fb_on) return fail("upr_batch_evaluate_policy: the batch was created with use_feedback_policy = 0");
     const upr_dims& d = h->d;
     if (eval_scratch(h)) return 1;
     std::vector<double> tt(h->B);
@@ -1325,7 +1433,7 @@ static int evaluate_core(upr_batch* h, const double* t, int t_stride, bool polic
     UPR_HIP(hipMemcpyAsync(h->ev_t, tt.data(), sizeof(double) * h->B, hipMemcpyHostToDevice, h->stream));
     if (policy) {
         UPR_HIP(hipMemcpyAsync(h->ev_xo, x_obs, sizeof(double) * h->B * d.nx, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(evaluate_policy_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->fb, h->ev_t, h->ev_xo, h->ev_x, h->ev_u);
+        if (launch_policy(h, h->ev_t, h->ev_xo)) return 1;
     } else hipLaunchKernelGGL(evaluate_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->ev_t, 1, h->ev_x, h->ev_u);
     UPR_HIP(hipGetLastError());
     UPR_HIP(hipMemcpyAsync(x_out, h->ev_x, sizeof(double) * h->B * d.nx, hipMemcpyDeviceToHost, h->stream));
@@ -1335,8 +1443,10 @@ static int evaluate_core(upr_batch* h, const double* t, int t_stride, bool polic
 }
 
 static int get_feedback_core(upr_batch* h, double* K) {
-    if (!h->fb) return fail("upr_batch_get_feedback: the batch was created with use_feedback_policy = 0");
+    if (!h->fb_on) return fail("upr_batch_get_feedback: the batch was created with use_feedback_policy = 0");
     const upr_dims& d = h->d;
+    if (fb_keep(h)) return 1;   // the first request after an advance gathers the array; later ones only copy
+    if (!h->fb && dev_alloc(&h->fb, (size_t)h->B * d.N * d.nu * d.nx)) return 1;   // (no solve yet: zeros)
     UPR_HIP(hipStreamSynchronize(h->stream));
     UPR_HIP(hipMemcpy(K, h->fb, sizeof(double) * h->B * d.N * d.nu * d.nx, hipMemcpyDeviceToHost));
     return 0;
@@ -1365,6 +1475,8 @@ int upr_batch_hold_stats(upr_batch* h, int restore) {
     UPR_HIP(hipStreamSynchronize(h->stream));
     if (!restore) return snapshot_take(h, h->held);
     if (h->held.stats.empty()) return fail("upr_batch_hold_stats: nothing held on this handle");
+    if (fb_keep(h)) return 1;   // (the QP status the gains' readers consult is overwritten below)
+    UPR_HIP(hipStreamSynchronize(h->stream));
     if (snapshot_put_back(h, h->held)) return 1;
     h->held = upr_stats_snapshot();
     return 0;
@@ -1472,6 +1584,7 @@ int upr_batch_eq_input_jacobian(upr_batch* h, int inst, double* gu) {
 // linearise at the current trajectory and solve one QP there with the multiplier export (no synchronisation)
 static int kkt_launch(upr_batch* h) {
     if (h->qp.exported && !h->kkt && dev_alloc(&h->kkt, (size_t)h->B * h->qp.stride)) return 1;
+    if (fb_keep(h)) return 1;   // (records, workspace and statistics of the advance's last QP are overwritten below)
     if (launch_linearize(h, traj_lin_args(h))) return 1;
     upr_qp_args A = make_qp_args(h);
     if (h->qp.exported) { A.kkt = h->kkt; A.kkt_stride = h->qp.stride; }
@@ -1480,6 +1593,7 @@ static int kkt_launch(upr_batch* h) {
 
 static int qp_step_core(upr_batch* h, double* dxs, double* dus) {
     const upr_dims& d = h->d;
+    if (fb_keep(h)) return 1;   // (as kkt_launch)
     if (launch_linearize(h, traj_lin_args(h))) return 1;
     if (launch_qp(h, make_qp_args(h))) return 1;
     UPR_HIP(hipStreamSynchronize(h->stream));
@@ -1995,7 +2109,7 @@ int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x,
         UPR_HIP(hipMemcpyAsync(h->t0, pt, sizeof(double) * n_in, hipMemcpyHostToDevice, h->stream));
         if (advance_impl(h)) return 1;
         // the policy at the observation: time t0, state x0 (both already on the device)
-        if (h->fb) hipLaunchKernelGGL(evaluate_policy_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->fb, h->t0, h->x0, h->ev_x, h->ev_u);
+        if (h->fb_on) { if (launch_policy(h, h->t0, h->x0)) return 1; }
         else hipLaunchKernelGGL(evaluate_kernel, dim3(h->B), dim3(64), 0, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->t0, 1, h->ev_x, h->ev_u);
         UPR_HIP(hipGetLastError());
         UPR_HIP(hipMemcpyAsync(ox, h->ev_x, sizeof(double) * (B * nx + B * nu), hipMemcpyDeviceToHost, h->stream));
@@ -2008,15 +2122,19 @@ int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x,
     const int sqp_now = h->sqp_iters_next > 0 ? h->sqp_iters_next : h->P.sqp_iters;
     unsigned long long sig = 1469598103934665603ull;
     for (unsigned long long v : {(unsigned long long)h->has_prev, (unsigned long long)h->guess_set, (unsigned long long)sqp_now, (unsigned long long)(h->order_on && h->order_valid),
-                                 (unsigned long long)(h->fb != nullptr), (unsigned long long)h->qp.fb_fused, (unsigned long long)h->timing, (unsigned long long)(stats_out != nullptr),
+                                 (unsigned long long)h->fb_on, (unsigned long long)h->qp.fb_fused, (unsigned long long)h->fbt.mode /* (with sqp_now: which policy kernel the period enqueues) */, (unsigned long long)h->timing, (unsigned long long)(stats_out != nullptr),
                                  (unsigned long long)h->qp.structure, (unsigned long long)h->qp.source, (unsigned long long)h->qp.nt, (unsigned long long)(uintptr_t)h->pin,
                                  (unsigned long long)(uintptr_t)h->prof /* (passed BY VALUE in upr_qp_args: a graph captured before upr_batch_qp_profile allocated it would keep nullptr) */,
                                  (unsigned long long)h->vf_track /* (one more kernel node and one more copy node in the period) */}) { sig ^= v; sig *= 1099511628211ull; }
-    const bool steady = h->tick_graph_on && !h->timing && h->has_prev && !h->guess_set && h->sqp_iters_next == 0 && (!h->order_on || h->order_valid);
+    // (... and, with the feedback policy, gains that are in the factors: the period then gathers and allocates nothing, and its policy
+    //  kernel is the one every later period enqueues)
+    const bool steady = h->tick_graph_on && !h->timing && h->has_prev && !h->guess_set && h->sqp_iters_next == 0 && (!h->order_on || h->order_valid) &&
+                        (!h->fb_on || upr_fb_capturable(h->fbt, sqp_now));
     if (steady && h->tick_exec && sig == h->tick_sig) {
         UPR_HIP(hipGraphLaunch(h->tick_exec, h->stream));
         // (what advance_impl does on the host besides enqueueing)
         h->hdyn_prev = h->hdyn0;
+        if (h->fb_on) h->fbt.state = upr_fb_on_replay(h->fbt, sqp_now, h->qp.fb_fused);
         if (h->vf_track && sqp_now > 0) { h->vf_state = 1; h->vf_tracked = true; }
         ++h->tick_replays;
     } else {
