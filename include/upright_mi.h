@@ -494,8 +494,31 @@ int upr_batch_path_accel_margin_points(upr_batch* h, int n, const double* x, int
                                        double d_max, double speed, double* accel, double* z, double* y, int* iters);
 int upr_batch_path_accel_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double d_max, double speed,
                                      double* accel, int* iters, double* window, int* knot, double* limit);
-/* device time (ms) of the kernel launches of the last balance check, friction margin, speed margin or path-acceleration margin on the
- * handle, HIP events around them (copies excluded) */
+/* ------------------------------------------------------------------------------------------------
+ * Retiming on a speed lattice (upright_amd/csrc/upr_retime.h): the fastest time law s(t) that replays the geometric path of the current
+ * plan with the objects balanced at every knot.  speeds[n_lvl]: the lattice s_0 < s_1 < .., finite, >= 0, 1 <= n_lvl <= 32.  A time
+ * law gives every knot i = 0 .. N a level m_i; sddot is constant on every segment: d_i = (s_{m_{i+1}}^2 - s_{m_i}^2) / (2 dt), the
+ * segment lasts 2 dt / (s_{m_i} + s_{m_{i+1}}), and an edge whose two speeds sum to 0 does not exist.  Edge (i, m -> m') is admissible
+ * in a scenario iff the departing state x_i(s_m, d) and the arriving state x_{i+1}(s_m', d), x(s, d) = (q, s v, s^2 a + d v), are both
+ * accepted by the rule of the margins above (rho <= 1e-8 max(|b|, 1) on the cold projection) and, with boxes != 0, s v and s^2 a + d v
+ * of every joint lie inside the velocity and acceleration boxes of the problem at both ends (positions do not move; jerk is not
+ * enforced: a step of sddot at a knot is an impulse of jerk).  The optimum is exact on the lattice: T[N][m] = 0 (only for end_level
+ * when it is >= 0), T[i][m] = min over admissible m' of the segment's time + T[i + 1][m'], ties to the smallest m'; the law starts at
+ * start_level, or (-1) at the level with the smallest T[0][.], ties to the smallest.
+ *       duration  T at the start; +inf when no time law exists on the lattice
+ *       level     [N + 1] the levels of the optimal law; all -1 when duration is infinite
+ *       reach     (f, g): f the last knot with a non-empty set of levels reachable forward from the start, g the first knot that
+ *                 has a level with finite T; (N, 0) for a feasible plan
+ *       edges     the masks, bit m' of row (segment i, level m): the edge m -> m' is admissible;  iters: the least-squares solves of
+ *                 a mask row (at most 2 n_lvl projections)
+ *   params as upr_batch_speed_margin_plan.  common == 0: duration[B][n_scen], level[B][n_scen][N+1], reach[B][n_scen][2]; common != 0:
+ *   one time law per instance that holds under every scenario (an edge must be admissible in all of them): duration[B], level[B][N+1],
+ *   reach[B][2].  edges[B][n_scen][N][n_lvl] and iters[B][n_scen][N][n_lvl] are per scenario in both cases.  NULL outputs are not
+ *   copied; duration and level must not both be NULL.  Scratch, timing and the state of the handle as the friction margin above. */
+int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, int start_level,
+                          int end_level, int common, int boxes, double* duration, int* level, int* reach, unsigned* edges, int* iters);
+/* device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin or retiming
+ * on the handle, HIP events around them (copies excluded) */
 double upr_batch_balance_ms(upr_batch* h);
 
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):

@@ -38,6 +38,7 @@
 #include "upr_margin.h"
 #include "upr_speed.h"
 #include "upr_pathacc.h"
+#include "upr_retime.h"
 #include "upr_iface.h"
 
 namespace {
@@ -934,7 +935,7 @@ int advance_impl(upr_batch* h) {
     return 0;
 }
 
-// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h): the fourteen entry points end here, in balance_call.  An entry fills a REQUEST, which
+// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h): the fifteen entry points end here, in balance_call.  An entry fills a REQUEST, which
 // names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
 // go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
 // the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
@@ -944,8 +945,8 @@ int advance_impl(upr_batch* h) {
 // that serves nothing else and only grows (bal_buf): a call in the steady state allocates and frees nothing.
 enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
 // the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h) | the
-// path-acceleration margin (upr_pathacc.h)
-enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4 };
+// path-acceleration margin (upr_pathacc.h) | the retiming of a plan on a speed lattice (upr_retime.h)
+enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5 };
 struct bal_request {
     const char* who = "";     // the entry, as its messages name it
     const char* needs = "";   // ... and what they say about its required pointers
@@ -966,6 +967,11 @@ struct bal_request {
     // the path-acceleration margin: out is accel, four doubles per job, certificates and reductions as the speed margin's; the range
     // [-d_max, d_max] of sddot at sdot = speed; limit [B][2] the interval of sddot the acceleration boxes allow
     double d_max = 0.0, speed = 1.0;
+    // the retiming (plan only): the lattice speeds [n_lvl]; start / end a level or -1; common: one time law under all scenarios;
+    // boxes: the velocity and acceleration boxes cut edges.  out is duration, one double per (instance, scenario) or per instance
+    // with common; level [..][N + 1], reach [..][2]; edges [B][n_scen][N][n_lvl] and iters, one per mask row, stay per scenario
+    const double* speeds = nullptr; int n_lvl = 0, start = -1, end = -1; bool common = false, boxes = true;
+    int *level = nullptr, *reach = nullptr; unsigned* edges = nullptr;
     // the answers on the host; all but the required ones may be NULL.  worst / worst_knot ([B][n_scen][n_grp]; plan, per group): the
     // largest kappa_hi over the knots of an instance, reduced on the device; out may then be NULL and kappa_hi stays on the device
     double* out = nullptr;   // rho | kappa_hi
@@ -1011,7 +1017,7 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
         return fail("path-acceleration margin: d_max must be finite and > 0, speed finite and >= 0");
     if (r.quantity == BAL_MARGIN_GROUPS && balance_check_groups(h, r.n_grp, r.group_mask)) return 1;
     if (!r.plan && r.n <= 0) return 2;
-    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst)) return refuse(r.needs);
+    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst && !r.level)) return refuse(r.needs);
     if (r.plan && !r.params) {
         if (r.n_scen != 1) return refuse("params == NULL needs n_scen == 1 (every instance's own body parameters)");
     } else if (r.n_scen < 1) return refuse("n_scen must be >= 1");
@@ -1021,28 +1027,38 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
     if (balance_check_scales(r.mu_base, (size_t)r.n_scen * d.nc, "mu_base")) return 1;
     const long long n = bal_points(h, r);
     if (n > (1ll << 31) - 64 || n * r.n_scen * r.n_grp > (1ll << 36)) return fail("balance check: too many points");
+    if (r.quantity == BAL_RETIME) {
+        bool ok = r.speeds && r.n_lvl >= 1 && r.n_lvl <= UPR_RET_MAX_LEVELS;
+        for (int m = 0; ok && m < r.n_lvl; ++m) ok = std::isfinite(r.speeds[m]) && r.speeds[m] >= 0 && (m == 0 || r.speeds[m] > r.speeds[m - 1]);
+        if (!ok) return fail("retime: speeds must be 1 .. 32 finite values >= 0 in strictly increasing order");
+        if (r.start < -1 || r.start >= r.n_lvl || r.end < -1 || r.end >= r.n_lvl) return fail("retime: start and end must be -1 or a level index");
+        if (n * r.n_scen * r.n_lvl > (1ll << 36)) return fail("balance check: too many points");   // (the jobs: a mask row each)
+    }
     return 0;
 }
 
 // form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
-// group, the speed margin, the path-acceleration margin.  Every kernel takes (its record, upr_bal_dims, long long jobs); the record is
-// upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the groups, upr_spd_args for the speed margin and upr_pac_args for
-// the path-acceleration margin.
-const void* const bal_kernels[2][7] = {
+// group, the speed margin, the path-acceleration margin, the edge masks of the retiming.  Every kernel takes (its record, upr_bal_dims,
+// long long jobs); the record is upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the groups, upr_spd_args for the
+// speed margin, upr_pac_args for the path-acceleration margin and upr_ret_args for the retiming.
+const void* const bal_kernels[2][8] = {
     /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
                     (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel,
-                    (const void*)upr_bal_pathacc1_kernel},
+                    (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel},
     /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
                     (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel,
-                    (const void*)upr_bal_pathacc_kernel}};
+                    (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel}};
 struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
 
 int balance_launch(upr_batch* h, const bal_request& r) {
     const upr_dims& d = h->d;
     upr_bal_dims L = h->bal.L;
     const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, speed = r.quantity == BAL_SPEED || pathacc;   // (speed: the four-double layout)
-    const bool margin = r.quantity != BAL_RHO && !speed, groups = r.quantity == BAL_MARGIN_GROUPS;
-    const long long n = bal_points(h, r), njobs = n * r.n_scen, ng = r.n_grp, nout = njobs * ng;
+    const bool retime = r.quantity == BAL_RETIME;
+    const bool margin = r.quantity != BAL_RHO && !speed && !retime, groups = r.quantity == BAL_MARGIN_GROUPS;
+    // (the retiming: a job is a mask row, (instance, scenario, segment, level); nplans outputs of the path kernel)
+    const long long n = bal_points(h, r), njobs = retime ? (long long)h->B * r.n_scen * d.N * r.n_lvl : n * r.n_scen, ng = r.n_grp, nout = njobs * ng;
+    const long long nplans = retime ? (long long)h->B * (r.common ? 1 : r.n_scen) : 0;
     const bool want_worst = r.worst || r.worst_knot;
     const long long nworst = want_worst ? (long long)h->B * r.n_scen * (speed ? 2 : ng) : 0;
     const size_t per_out = speed ? 4 : 1, ends = speed ? 2 : 1;   // doubles of `out` and certificates per job
@@ -1058,7 +1074,7 @@ int balance_launch(upr_batch* h, const bal_request& r) {
         return o;
     };
     const size_t o_st = region(sizeof(double) * n * UPR_BAL_ST, true, nullptr, nullptr);
-    const size_t o_rho = region(sizeof(double) * nout * per_out, true, nullptr, r.out);
+    const size_t o_rho = region(sizeof(double) * (retime ? nplans : nout * per_out), true, nullptr, r.out);
     const size_t o_z = region(sizeof(double) * nout * ends * L.ncol, r.z != nullptr, nullptr, r.z);
     const size_t o_it = region(sizeof(int) * nout, r.iters != nullptr, nullptr, r.iters);
     const size_t o_par = region(sizeof(double) * bal_param_sets(h, r) * d.nb * 10, r.params != nullptr, r.params, nullptr);
@@ -1070,7 +1086,12 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const size_t o_w = region(sizeof(double) * nworst, want_worst, nullptr, r.worst);
     const size_t o_wk = region(sizeof(int) * nworst, want_worst, nullptr, r.worst_knot);
     const size_t o_lim = region(sizeof(double) * h->B * (pathacc ? 2 : 1), r.limit != nullptr, nullptr, r.limit);
-    const size_t o_vee = region(sizeof(double) * n * 3, pathacc, nullptr, nullptr);
+    const size_t o_vee = region(sizeof(double) * n * 3, pathacc || retime, nullptr, nullptr);
+    const size_t o_spd = region(sizeof(double) * r.n_lvl, retime, r.speeds, nullptr);
+    const size_t o_edg = region(sizeof(unsigned) * nout, retime, nullptr, r.edges);
+    const size_t o_arg = region((size_t)nplans * d.N * r.n_lvl, retime, nullptr, nullptr);
+    const size_t o_lvl = region(sizeof(int) * nplans * (d.N + 1), retime, nullptr, r.level);
+    const size_t o_rch = region(sizeof(int) * nplans * 2, retime && r.reach, nullptr, r.reach);
     if (balance_scratch(h, total)) return 1;
     char* base = (char*)h->bal_buf;
     for (int i = 0; i < nup; ++i) UPR_HIP(hipMemcpyAsync(base + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, h->stream));
@@ -1079,8 +1100,8 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const double* dx = r.plan ? h->xs : (const double*)(base + o_x);
     double *dst = (double*)(base + o_st), *drho = (double*)(base + o_rho);
     const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
-    if (pathacc && h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_vee_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
-    else if (pathacc) hipLaunchKernelGGL(upr_bal_state_vee_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
+    if ((pathacc || retime) && h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_vee_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
+    else if (pathacc || retime) hipLaunchKernelGGL(upr_bal_state_vee_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
     else if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
     else hipLaunchKernelGGL(upr_bal_state_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
     UPR_HIP(hipGetLastError());
@@ -1102,6 +1123,11 @@ int balance_launch(upr_batch* h, const bal_request& r) {
         C.J = A; C.J.rho = nullptr; C.d_max = r.d_max; C.speed = r.speed; C.vee = (const double*)(base + o_vee); C.accel = drho;
         C.y = r.y ? (double*)(base + o_y) : nullptr;
     }
+    upr_ret_args T;
+    if (retime) {
+        T.J = A; T.J.rho = nullptr; T.vee = (const double*)(base + o_vee); T.xs = dx; T.speeds = (const double*)(base + o_spd); T.M = r.n_lvl;
+        T.nk = d.N + 1; T.nx = d.nx; T.boxes = r.boxes ? 1 : 0; T.h = h->P.dt; T.edges = (unsigned*)(base + o_edg);
+    }
     upr_grp_args X;
     if (groups) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = r.mu_base ? (const double*)(base + o_mu) : nullptr; }
     // lane form: 64 jobs per workgroup, the groups on the y axis.  Wave form: a workgroup is one wave and the jobs (for the groups:
@@ -1109,9 +1135,15 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     // the largest shape share a CU inside the 160 KiB)
     long long count = (wave && groups) ? nout : njobs;
     const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
-    void* args[] = {pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
+    void* args[] = {retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
     UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
-    if (pathacc && (want_worst || r.limit)) {
+    if (retime) {
+        upr_ret_path_args Q;
+        Q.edges = T.edges; Q.speeds = T.speeds; Q.M = r.n_lvl; Q.nk = d.N + 1; Q.n_scen = r.n_scen; Q.common = r.common ? 1 : 0; Q.start = r.start; Q.end = r.end;
+        Q.h = h->P.dt; Q.arg = (unsigned char*)(base + o_arg); Q.duration = drho; Q.level = (int*)(base + o_lvl); Q.reach = r.reach ? (int*)(base + o_rch) : nullptr;
+        hipLaunchKernelGGL(upr_bal_retime_path_kernel, dim3((unsigned)(nplans < 16384 ? nplans : 16384)), dim3(64), 0, h->stream, Q, nplans);
+        UPR_HIP(hipGetLastError());
+    } else if (pathacc && (want_worst || r.limit)) {
         const long long lanes = nworst + (r.limit ? h->B : 0);
         hipLaunchKernelGGL(upr_bal_pathacc_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
                            d.N + 1, r.n_scen, nworst, h->B, d.nx, r.speed, (const double*)h->xs, (double*)(base + o_w),
@@ -1916,6 +1948,14 @@ int upr_batch_path_accel_margin_plan(upr_batch* h, int n_scen, const double* par
     return balance_call(h, {.who = "upr_batch_path_accel_margin_plan", .needs = "accel and window must not both be NULL", .plan = true, .n_scen = n_scen,
                             .params = params, .per = per_instance != 0, .quantity = BAL_PATHACC, .limit = limit, .d_max = d_max, .speed = speed, .out = accel,
                             .iters = iters, .worst = window, .worst_knot = knot});
+}
+
+int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, int start_level, int end_level,
+                          int common, int boxes, double* duration, int* level, int* reach, unsigned* edges, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_retime_plan", .needs = "duration and level must not both be NULL", .plan = true, .n_scen = n_scen, .params = params,
+                            .per = per_instance != 0, .quantity = BAL_RETIME, .speeds = speeds, .n_lvl = n_lvl, .start = start_level, .end = end_level,
+                            .common = common != 0, .boxes = boxes != 0, .level = level, .reach = reach, .edges = edges, .out = duration, .iters = iters});
 }
 
 double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }

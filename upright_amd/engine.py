@@ -18,6 +18,16 @@ def uptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint))
 
 
+def _level_of(speeds, s, what):
+    """the lattice level of the speed s (None: -1, free)"""
+    if s is None:
+        return -1
+    hit = np.flatnonzero(speeds == float(s))
+    if hit.size != 1:
+        raise ValueError("retime_plan: %s must equal a lattice speed" % what)
+    return int(hit[0])
+
+
 class BatchMPC:
     def __init__(self, problem, B=1, body_params=None, way_p=None, way_q=None, device=None):
         self.problem = problem.validate()
@@ -564,8 +574,78 @@ class BatchMPC:
             return w, knot, limit
         return self._asked_for(acc[..., 0::2].copy(), acc[..., 1::2].copy() if want_out else None, iters)
 
+    def retime_plan(self, speeds, params=None, start=None, end=None, common=False, boxes=True, want_reach=False, want_edges=False, want_iters=False):
+        """(duration, level): the fastest time law on the lattice `speeds` that replays the geometric path of the current plan with the
+        objects balanced at every knot (upr_batch_retime_plan), where speed_margin_plan could only offer one uniform factor.  speeds
+        (M,): replay speeds s_0 < s_1 < .., finite, >= 0, 1 <= M <= 32.  The law gives knot i the speed speeds[level[i]] and keeps
+        sddot constant on every segment: d_i = (s_{i+1}^2 - s_i^2) / (2 dt), the segment lasts 2 dt / (s_i + s_{i+1}); two speeds that sum
+        to 0 are no edge.  An edge is admissible in a scenario iff its departing state x_i(s_i, d_i) and its arriving state
+        x_{i+1}(s_{i+1}, d_i), x(s, d) = (q, s v, s^2 a + d v), are both balanced by the rule of path_accel_margin (rho <= 1e-8
+        max(|b|, 1)) and, with boxes, s v and s^2 a + d v of every joint stay inside the velocity and acceleration bounds of the problem
+        at both ends.  Positions do not move.  Jerk is NOT enforced: a step of sddot at a knot is an impulse of jerk.  The optimum
+        over the lattice is exact (a dynamic programme, ties to the smallest level).  start / end: the speed of the first / last
+        knot, which must equal a lattice value, or None: free.  params as in balance_check_plan.
+
+        duration (B, n_scen) in seconds, inf where no time law exists on the lattice; level (B, n_scen, N + 1) int32, -1 throughout
+        where duration is inf.  common=True: ONE time law per instance that holds under every scenario -- duration (B,), level (B,
+        N + 1).  With want_reach / want_edges / want_iters the tuple (duration, level, reach, edges, iters) restricted to what was
+        asked for: reach (.., 2) = (f, g), f the last knot with a level reachable forward from the start, g the first knot that has
+        a level from which the end can be reached -- (N, 0) for a feasible plan, where an infeasible one blocks from each side;
+        edges (B, n_scen, N, M) uint32, bit m' of row (i, m): the edge m -> m' of segment i is admissible in that scenario (per
+        scenario with common=True too: the law runs on their AND); iters, same shape, the least-squares solves of a mask row.
+        retimed_states(level, speeds) gives the times and states of the law.
+
+        The study's sweep (balance_check) as one braking law that holds under all 45 scenarios and ends at rest:
+
+            th = mpc.problem.body_params                      # (1, 10): [m, m c, vech(I)]
+            h = np.array([0.02, 0.02, 0.03])                  # half extents of the CoM box
+            offs = [np.zeros(3)] + [s * h[a] * np.eye(3)[a] for a in range(3) for s in (1, -1)] + [(2 * np.array(v) - 1) * h for v in np.ndindex(2, 2, 2)]
+            params = []
+            for d in offs:
+                for k in (1.0, 0.5, 0.1):
+                    p = th.copy(); p[:, 1:4] += p[:, :1] * d; p[:, 4:] *= k
+                    params.append(p)
+            speeds = np.linspace(0.0, 1.5, 13)
+            duration, level = mpc.retime_plan(speeds, np.stack(params), common=True, end=0.0)   # (B,), (B, N + 1)
+            t, dep, arr = mpc.retimed_states(level, speeds)   # knot times and the states on both sides of every segment
+        """
+        speeds = cont(speeds).reshape(-1)
+        n_scen, per_instance, params = self._plan_params(params)
+        lead = (self.B,) if common else (self.B, n_scen)
+        dur, level, reach = self._outputs(lead, (True, (), F8), (True, (self.N + 1,), I4), (want_reach, (2,), I4))
+        edges, iters = self._outputs((self.B, n_scen, self.N, speeds.size), (want_edges, (), np.uint32), (want_iters, (), I4))
+        check(self._lib.upr_batch_retime_plan(self._h, n_scen, ptr(params), per_instance, int(speeds.size), ptr(speeds), _level_of(speeds, start, "start"),
+                                              _level_of(speeds, end, "end"), int(bool(common)), int(bool(boxes)), ptr(dur), iptr(level), iptr(reach),
+                                              uptr(edges) if want_edges else None, iptr(iters)))
+        return self._asked_for(dur, level, reach, edges, iters)
+
+    def retimed_states(self, level, speeds):
+        """(t, dep, arr) of the time laws `level` (.., N + 1) of retime_plan on the current plan (solution()), leading axes (B,) or (B,
+        n_scen): t (.., N + 1) the knot times, the cumulative 2 dt / (s_i + s_{i+1}); dep (.., N, 3 nq) the state in which knot i
+        departs on segment i, (q_i, s_i v_i, s_i^2 a_i + d_i v_i); arr (.., N, 3 nq) the state in which knot i + 1 arrives from it,
+        (q_{i+1}, s_{i+1} v_{i+1}, s_{i+1}^2 a_{i+1} + d_i v_{i+1}).  NaN where the plan has no time law (level -1).  Plain numpy."""
+        speeds = np.asarray(speeds, dtype=np.float64).reshape(-1)
+        level = np.asarray(level)
+        _, xs, _ = self.solution()
+        nq, dt = self.problem.nq, float(self.problem.dt)
+        x = xs[..., :3 * nq]
+        if level.ndim == 3:
+            x = np.broadcast_to(x[:, None], level.shape[:2] + x.shape[1:])
+        ok = (level >= 0).all(axis=-1)
+        s = np.where(level >= 0, speeds[np.maximum(level, 0)], np.nan)
+        s0, s1 = s[..., :-1], s[..., 1:]
+        d = (s1 - s0) * (s1 + s0) / (2.0 * dt)
+        t = np.zeros(level.shape)
+        t[..., 1:] = np.cumsum(2.0 * dt / (s0 + s1), axis=-1)
+        t[~ok] = np.nan
+
+        def side(xk, sk):
+            q, v, a = xk[..., :nq], xk[..., nq:2 * nq], xk[..., 2 * nq:]
+            return np.concatenate([q + 0.0 * sk[..., None], sk[..., None] * v, (sk * sk)[..., None] * a + d[..., None] * v], axis=-1)
+        return t, side(x[..., :-1, :], s0), side(x[..., 1:, :], s1)
+
     def balance_ms(self):
-        """Device time (ms) of the kernel launches of the last balance check, friction margin, speed margin or path-acceleration margin
+        """Device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin or retiming
         (HIP events around them)."""
         return float(self._lib.upr_batch_balance_ms(self._h))
 
