@@ -4,6 +4,5 @@
 #   tools/build_prof.sh && gpurun -- 'UPR_LIB=libupright_mi_prof.so python tools/dbg_profile.py 1024 256 mat'
 set -e
 cd "$(dirname "$0")/.."
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-value -DUPR_MONOLITHIC -DUPR_QP3_PROF -DUPR_QP3_PROF_MAT \
-    -o upright_amd/libupright_mi_prof.so upright_amd/csrc/upr_api.hip -lhiprtc -ldl
+python -c 'from __graft_entry__ import build_engine; build_engine(out="upright_amd/libupright_mi_prof.so", extra_flags=["-DUPR_MONOLITHIC", "-DUPR_QP3_PROF", "-DUPR_QP3_PROF_MAT"])'
 ls -l upright_amd/libupright_mi_prof.so

@@ -1,7 +1,7 @@
 """Phase stamps of the line-search kernel (library built with -DUPR_LS_PROF, loaded through UPR_LIB): cycles of
 [staging + baseline pass + first reduction | second reduction | trial evaluations | (statistics)] per instance, in the QP-residual slots.
-Build:  cd upright_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DUPR_LS_PROF -c upr_api.hip -o /tmp/api_lsprof.o
-        hipcc --offload-arch=gfx950 -shared -fPIC -o ../libupright_mi_lsprof.so /tmp/api_lsprof.o build/upr_qp3_part*.o -lhiprtc -ldl
+Build:  python -c 'from __graft_entry__ import build_engine; build_engine(out="upright_amd/libupright_mi_lsprof.so", extra_flags=["-DUPR_LS_PROF"], qp3_parts=False)'
+        (the units of the C-ABI alone; the production QP kernel's objects are linked as the last full build left them)
 Run:    gpurun -- 'UPR_LIB=libupright_mi_lsprof.so python3 tools/dbg_ls_phases.py headline'
 Round 4 (headline, B = 1024): 46 k cycles staging + baseline pass, 43 k the one trial evaluation (joint sines / cosines + chain walk, a lane
 per knot), 4 k the rest, of the 141 k cycles (0.059 ms) the kernel lasts; the remainder is its prologue (dispatch-order ranking, problem record to LDS)."""

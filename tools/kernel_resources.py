@@ -1,20 +1,22 @@
 #!/usr/bin/env python3
-"""Resource usage of every ahead-of-time instantiation of the production QP kernel (and of upr_api.hip's kernels with `api`):
-VGPRs, spilled VGPRs, scratch bytes, LDS, occupancy -- from the compiler's kernel-resource-usage remarks (no GPU needed).
+"""Resource usage of every ahead-of-time instantiation of the production QP kernel (and of the kernels of the C-ABI's units,
+__graft_entry__.ENGINE_UNITS, with `api`): VGPRs, spilled VGPRs, scratch bytes, LDS, occupancy -- from the compiler's
+kernel-resource-usage remarks (no GPU needed).
     python tools/kernel_resources.py [part ...| api] [-DUPR_...]"""
+import os
 import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
-CSRC = Path(__file__).resolve().parents[1] / "upright_amd" / "csrc"
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from __graft_entry__ import CSRC, ENGINE_UNITS, HIPCC_FLAGS  # noqa: E402
 
 
-def usage(part, extra=()):
-    src = "upr_api.hip" if part == "api" else "upr_qp3_inst.hip"
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed", *extra,
-           *([] if part == "api" else [f"-DUPR_QP3_PART={part}"]), "--cuda-device-only", "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
+def usage_of(src, extra=()):
+    """the remarks of one translation unit: {kernel symbol: {vgpr, agpr, spill, scratch, lds, occ}}"""
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *HIPCC_FLAGS, *extra, "--cuda-device-only", "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
     r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True)
     out, name = {}, None
     for line in r.stderr.splitlines():
@@ -26,6 +28,17 @@ def usage(part, extra=()):
             m = re.search(pat, line)
             if m and name:
                 out[name][key] = int(m.group(1))
+    return out
+
+
+def usage(part, extra=()):
+    """`api`: the merged table of the units of the C-ABI, compiled side by side (at most 8 at once); else part `part` of the production QP kernel"""
+    if part != "api":
+        return usage_of("upr_qp3_inst.hip", (*extra, f"-DUPR_QP3_PART={part}"))
+    out = {}
+    with ThreadPoolExecutor(max(1, min(len(ENGINE_UNITS), 8, os.cpu_count() or 1))) as ex:
+        for r in ex.map(lambda u: usage_of(u, extra), ENGINE_UNITS):
+            out.update(r)
     return out
 
 

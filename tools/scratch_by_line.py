@@ -1,4 +1,4 @@
-"""Where a kernel's scratch traffic sits: compiles one part of the production QP kernel (or upr_api.hip with 'api') for gfx950 with line
+"""Where a kernel's scratch traffic sits: compiles one part of the production QP kernel (or the units of the C-ABI with 'api') for gfx950 with line
 tables and counts scratch_load / scratch_store instructions per kernel and per 25-line bucket of the source.  A spill COUNT says
 little; a register array that LIVES in scratch shows up here as stores right behind its loads and reloads at every use
 (DESIGN.md "Registers that lived in scratch").   python tools/scratch_by_line.py <part 0..6 | api> [top N] [extra -D flags ...]"""
@@ -6,14 +6,14 @@ import collections, os, re, subprocess, sys, tempfile
 part = sys.argv[1] if len(sys.argv) > 1 else "0"
 top = int(sys.argv[2]) if len(sys.argv) > 2 else 12
 extra = sys.argv[3:]
-root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "upright_amd", "csrc")
-src = "upr_api.hip" if part == "api" else "upr_qp3_inst.hip"
-out = os.path.join(tempfile.gettempdir(), "scratch_by_line_%s.s" % part)
-cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed",
-       "-gline-tables-only", "-S", "--cuda-device-only", src, "-o", out] + ([] if part == "api" else ["-DUPR_QP3_PART=" + part]) + extra
-subprocess.run(cmd, cwd=root, check=True, stderr=subprocess.DEVNULL)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from __graft_entry__ import CSRC, ENGINE_UNITS, HIPCC_FLAGS, run_side_by_side
+srcs = ENGINE_UNITS if part == "api" else ("upr_qp3_inst.hip",)   # ('api': every unit of the C-ABI, side by side)
+outs = [os.path.join(tempfile.gettempdir(), "scratch_by_line_%s_%d.s" % (part, i)) for i in range(len(srcs))]
+run_side_by_side([[os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *HIPCC_FLAGS, "-gline-tables-only", "-S", "--cuda-device-only", str(CSRC / s), "-o", o]
+                  + ([] if part == "api" else ["-DUPR_QP3_PART=" + part]) + extra for s, o in zip(srcs, outs)])
 files, cnt, cur, fn = {}, collections.defaultdict(collections.Counter), None, None
-for l in open(out):
+for l in (l for o in outs for l in open(o)):
     m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
     if m: files[m.group(1)] = (m.group(3) or m.group(2)); continue
     m = re.match(r'^(_Z\w+):', l)

@@ -1,5 +1,11 @@
 // upr_api.hip -- C-ABI of libupright_mi.so (include/upright_mi.h): host orchestration of the HIP kernels.
 // No CPU compute path: every entry point that computes launches kernels on the current HIP device.
+// This unit: the handle's lifecycle, advance_impl, tick and its graph, the solution / evaluate / feedback / KKT / value-function
+// entries, the run-time instantiation of the production QP kernel (jit_get), and the small kernels (prepare, evaluate*, feedback,
+// core_*, those of upr_value.h).  The handle and the error plumbing are upr_handle.h's; it defines upr_fail for every unit.
+// What crosses its boundary (declared in upr_handle.h): it calls upr_bal_resolve (upr_api_balance.hip: the balance family and its
+// entries), upr_launch_resolve / launch_linearize / launch_linesearch (upr_api_launch.hip) and qp_generic_launcher / qp2_launcher
+// (upr_api_qp_old.hip); of upr_qp.h / upr_qp2.h it reads the host-side layouts only and instantiates no kernel.
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
@@ -20,64 +26,21 @@
 #include <string>
 #include <vector>
 
-#include "upr_common.h"
-#include "upr_kin.h"
-#include "upr_linearize.h"
-#include "upr_linearize2.h"
-#include "upr_linesearch.h"
-#include "upr_qp.h"
-#include "upr_qp2.h"
-#include "upr_qp3.h"
-#include "upr_qp3_list.h"
+#include "upr_handle.h"
 #include "upr_qp3_launch.h"
-#include "upr_qp_select.h"
-#include "upr_fb_state.h"
-#include "upr_launch_select.h"
 #include "upr_value.h"
-#include "upr_balance.h"
-#include "upr_margin.h"
-#include "upr_speed.h"
-#include "upr_pathacc.h"
-#include "upr_retime.h"
 #include "upr_iface.h"
 
 namespace {
+thread_local std::string g_err;   // the calling thread's last error (upr_last_error)
+}  // namespace
 
-thread_local std::string g_err;
-
-int fail(const std::string& msg) {
+int upr_fail(const std::string& msg) {
     g_err = msg;
     return 1;
 }
 
-#define UPR_HIP(call)                                                                                 \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(e_) + " (upr_api.hip:" + std::to_string(__LINE__) + ")"); \
-    } while (0)
-
-// device scratch of one call: freed on every exit path (the early returns of UPR_HIP included)
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) {
-        UPR_HIP(hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)));
-        UPR_HIP(hipMemset(p, 0, (n ? n : 1) * sizeof(T)));
-        return 0;
-    }
-    operator T*() const { return p; }
-};
-
-template <class T>
-int dev_alloc(T** p, size_t n) {
-    UPR_HIP(hipMalloc((void**)p, n * sizeof(T)));
-    UPR_HIP(hipMemset(*p, 0, n * sizeof(T)));
-    return 0;
-}
+namespace {
 
 // ---- small kernels -----------------------------------------------------------------------------------
 __global__ void core_object_dynamics_kernel(const upr_problem* P, const double* body_params, int n, const double* forces,
@@ -140,16 +103,6 @@ __global__ void evaluate_kernel(const upr_problem* P, upr_dims d, int B, const d
     for (int i = threadIdx.x; i < nu; i += blockDim.x)
         upr_interp(d, P->dt, tsol[b], xs + (size_t)b * (N + 1) * nx, us + (size_t)b * N * nu, tau, 0, i, nullptr, u_out + (size_t)b * nu + i);
 }
-
-// Where the QP kernel that ran left its per-knot factors (doubles, relative to the instance workspace)
-struct upr_fb_src {
-    int kind;                       // 3: K stored; 1, 2: V = Lj^-1 Hux and Lji = Lj^-1 stored
-    long k_base; int k_stride;      // kind 3: K_k ; kinds 1, 2: V_k
-    long lji_base; int lji_stride;  // kinds 1, 2
-    long lfi_base; int lfi_stride;  // inverse Cholesky factor of the contact-force blocks of Hff
-    long lsi_base; int lsi_stride;  // inverse Cholesky factor of S = Df Hff^-1 Df'
-    int lsi_sb;                     // its block size: ne (one dense factor per knot) or 6 (star arrangements of the production kernel: one 6 x 6 block per body)
-};
 
 // Linear feedback gains of the last QP, ocs2 sign convention (u = bias + K x): fb[B][N][nu][nx].
 // Jerk rows: -Hjj^-1 Hux from the Riccati recursion; contact-force rows: -Hff^-1 Df' S^-1 C (the forces
@@ -300,161 +253,36 @@ __global__ void evaluate_policy_factors_kernel(const upr_problem* P, upr_dims d,
 }
 static_assert(2 * UPR_MAX_NU * UPR_MAX_NX * sizeof(double) <= 64 * 1024, "two knots of gains in the LDS a kernel gets without asking");
 
-}  // namespace
-
-// ========================================================================================================
-// every entry point that takes a handle: the handle's own device is made current for the calling thread (the HIP "current
-// device" is per thread; a stream may only be used with its device current), so that one process can hold engines on several
-// GPUs and a launcher's rank r runs on the GPU its engine was created on whatever another library selected in between
-#define UPR_ENTER(h) do { if (!(h)) return fail("null batch"); if ((h)->device >= 0) UPR_HIP(hipSetDevice((h)->device)); } while (0)
-
-// an instantiation of the production QP kernel made at run time (hiprtc; "run-time instantiation" further down)
-struct upr_jit_kernel {
-    hipModule_t mod = nullptr;
-    hipFunction_t fn = nullptr;
-    size_t lds = 0, ws = 0;
-    int nt = 256;       // lanes per workgroup (UPR_JIT_NT: 128 | 256 | 512, experiments)
-    std::string cfg;    // the template arguments, as rocprofv3 prints them
-    upr_fb_src fb{};    // where this instantiation leaves K, Lf^-1, Ls^-1, as its own info kernel reported them
-};
-
-// the QP kernel of a handle, resolved once at upr_batch_create: the record of upr_qp_select.h and what only this file knows
-struct upr_qp_sel : upr_qp_choice {
-    int (*launch)(struct upr_batch*, const upr_qp_args&) = nullptr;
-    upr_jit_kernel* jit = nullptr;   // production kernel from a run-time instantiation: its module function, nt and lds
-    upr_fb_src fb{};                 // where the kernel leaves its per-knot factors (kind 0 = no source: the feedback launch is refused)
-};
-
-// ... and its linearisation and line-search kernels (upr_launch_select.h), resolved there too: the record and the kernel it names
-struct upr_lin_sel : upr_lin_choice {
-    const void* kern = nullptr;   // upr_linearize_kernel<...>(A), or upr_linearize2_kernel<NQ>(A, kpw, n_sph) for kind 2
-    char name[128] = "";          // the instantiation with the workgroups of the last launch (upr_batch_lin_kernel_name)
-};
-struct upr_ls_sel : upr_ls_choice {
-    void (*kern)(upr_ls_args) = nullptr;
-    char name[128] = "";          // the instantiation, as rocprofv3 prints it (upr_batch_ls_kernel_name)
-};
-
-// ... and the form of its balance family (upr_balance.h, upr_margin.h; "balance family" further down)
-namespace {
-enum { BAL_LANE = 0, BAL_WAVE = 1 };
-struct upr_bal_choice {
-    upr_bal_dims L{};      // the layout of a job
-    size_t lds = 0;        // dynamic LDS of a workgroup of the wave form, bytes
-    int form = BAL_WAVE;   // BAL_LANE: a lane per job (one-body shapes); BAL_WAVE: a wave per job
-};
-// statistics and QP dispatch keys of a handle as the last advance left them, taken before a query solves one more QP on the handle
-// and put back behind it (snapshot_take / snapshot_put_back)
-struct upr_stats_snapshot {
-    std::vector<double> stats; std::vector<unsigned char> keys;
-};
-}  // namespace
-
-struct upr_batch {
-    upr_problem P;
-    upr_dims d;
-    int B = 0;
-    int device = -1;            // HIP device the handle's buffers and stream live on (the current device at upr_batch_create)
-    hipStream_t stream = nullptr;
-    upr_problem* dP = nullptr;
-    double *body_params = nullptr, *way_p = nullptr, *way_q = nullptr, *t0 = nullptr, *x0 = nullptr;
-    double *xs = nullptr, *us = nullptr, *xs_prev = nullptr, *us_prev = nullptr, *tprev = nullptr;
-    double *lin = nullptr, *Df = nullptr, *ws = nullptr, *stats = nullptr;
-    int *done = nullptr;
-    bool has_prev = false;   // a solution of a previous advance exists (warm start, policy evaluation)
-    unsigned char* iter_key = nullptr;   // [B] IPM iteration count of the last QP, one byte per instance (what `order` is ranked by)
-    int* order = nullptr;       // dispatch order of the QP launch: instances by the iteration count of their last QP, longest first
-    bool order_on = true, order_valid = false;
-    double* prof = nullptr;
-    double *ev_t = nullptr, *ev_xo = nullptr, *ev_x = nullptr, *ev_u = nullptr;   // scratch of the evaluate / evaluate_policy calls
-    double* kkt = nullptr;   // multiplier export of the register-resident QP kernel (upr_batch_qp_kkt), allocated on first use
-    // feedback gains (sqp.use_feedback_policy, fb_on): where those of the last advance are (upr_fb_state.h) and the array
-    // fb[B][N][nu][nx] they are gathered into -- allocated at create where UPR_FB_FUSED is set, at the first gather otherwise
-    bool fb_on = false;
-    upr_fb_track fbt;
-    double *fb = nullptr, *xs_lin = nullptr;
-    // dynamic obstacle (n_dyn == 1): observed state per instance (device + host copies, and the one the stored
-    // solution belongs to), activation flag of the projectile rows
-    double *dyn0 = nullptr, *pflag = nullptr;
-    std::vector<double> hdyn0, hdyn_prev;
-    double* pin = nullptr;   // pinned host staging of upr_batch_tick
-    // upr_batch_tick as a HIP graph: the eleven stream operations of a control period (three copies in, prepare, linearise, QP,
-    // line search, policy, three copies out) captured once the handle is in its steady state and replayed while that state --
-    // tick_sig: everything on the host that decides WHICH operations a tick enqueues -- stays the same
-    hipGraphExec_t tick_exec = nullptr;
-    unsigned long long tick_sig = 0;
-    int tick_steady = 0;        // ticks in a row with the same signature
-    int tick_graph_on = -1;     // UPR_TICK_GRAPH (default 1), read once
-    long long tick_replays = 0;
-    int nxf = 0;   // interface state dimension 3 nq + 9 n_dyn
-    bool guess_set = false;
-    int sqp_iters_next = 0;   // > 0: SQP iterations of the next advance only (init_sqp_iteration of the first solve)
-    double last_ms = 0.0;
-    upr_qp_sel qp;   // the QP kernel instantiation this handle launches
-    upr_lin_sel lin_sel;   // the linearisation kernel instantiation this handle launches
-    upr_ls_sel ls_sel;     // ... and the line-search one
-    int lin_blocks_last = -1;   // workgroups of the last linearisation launch (upr_batch_lin_kernel_name); -1: none yet
-    bool ls_launched = false;   // a line search was launched (upr_batch_ls_kernel_name)
-    int timing = 0;   // 0: no events; 1: around every kernel of an advance; 2: around the QP kernel only; 3: around every FOURTH QP launch
-    unsigned timing_qp_count = 0;   // QP launches since upr_batch_enable_timing (mode 3 samples those with count % 4 == 0)
-    double k_ms[3] = {0, 0, 0};
-    int k_launches[3] = {0, 0, 0};
-    std::vector<double> hDf;
-    upr_stats_snapshot held;   // upr_batch_hold_stats
-    std::vector<double> kkt_slack;   // slacks of the rows at the exit of the last upr_batch_qp_kkt ([B][N+1][ni]; upr_batch_qp_slacks)
-    std::vector<double> kkt_pairs;   // slack pairs of the softened rows of that QP, [3: sigma, tau, gam][B][N+1][ni] (upr_batch_qp_slack_pairs)
-    // value function of the last QP (upr_batch_value_function_update): cost-to-go matrices, gradients, cost-to-go of the plan and
-    // expansion points of every instance on the device, and the time of knot 0 of the plan they belong to
-    double *vf_P = nullptr, *vf_p = nullptr, *vf_J = nullptr, *vf_X = nullptr, *vf_t0 = nullptr;
-    int vf_state = 0;        // 0: no update yet; 1: current; 2: stale (the plan or the observation changed since)
-    double vf_ms = 0.0;      // device time of the last cost-to-go launch
-    hipEvent_t vf_ev[2] = {nullptr, nullptr};
-    double* vf_nu = nullptr;   // [B][N][ne] equality multipliers of that QP (the cost-to-go kernel's copy: upr_batch_equality_lagrangian)
-    // tracked mode (upr_batch_track_value_function): the advance hands its own last QP to the cost-to-go kernel in-stream.
-    // vf_tracked: the current cost-to-go came from an advance -- it belongs to the solve and outlives upr_batch_set_observation
-    bool vf_track = false, vf_tracked = false;
-    bool vf_ms_pending = false;   // events of a tracked launch on a timed handle recorded, vf_ms not read back yet
-    // balance check (upr_balance.h): HIP events around the two launches of the last call and their distance (upr_batch_balance_ms)
-    hipEvent_t bal_ev[2] = {nullptr, nullptr};
-    double bal_ms = 0.0;
-    void* bal_buf = nullptr; size_t bal_cap = 0;   // scratch of the balance-check calls, grown on demand, used for nothing else
-    upr_bal_choice bal;   // the form of the balance family's kernels on this handle
-    std::vector<hipEvent_t> ev_pool, ev_free;   // events in use (pairs, in launch order) / harvested ones waiting for reuse
-    std::vector<int> ev_slot;
-};
-
-namespace {
-
 int check_problem(const upr_problem* P) {
-    if (!P) return fail("upr_problem is NULL");
-    if (P->nq != 6 && P->nq != 9) return fail("unsupported chain length nq = " + std::to_string(P->nq) + " (kernels are instantiated for 6 and 9 joints)");
-    if (P->nb < 1 || P->nb > UPR_MAX_BODIES) return fail("nb out of range");
-    if (P->nc < 1 || P->nc > UPR_MAX_CONTACTS) return fail("nc out of range");
-    if (P->nf != 1 && P->nf != 3) return fail("nf must be 1 or 3");
-    if (P->N < 1 || P->N > 1000) return fail("N out of range");
-    if (!(P->dt > 0)) return fail("dt must be positive");
-    if (P->n_way < 1 || P->n_way > UPR_MAX_WAYPOINTS) return fail("n_way out of range");
-    for (int i = 0; i < 6; ++i) if (!(P->Wee[i] >= 0)) return fail("end-effector weights must be non-negative");
-    if (P->n_sph < 0 || P->n_sph > UPR_MAX_SPHERES) return fail("n_sph out of range");
-    if (P->n_pairs < 0 || P->n_pairs > UPR_MAX_PAIRS) return fail("n_pairs out of range");
-    if (P->n_dyn < 0 || P->n_dyn > UPR_MAX_DYN) return fail("n_dyn must be in 0 .. UPR_MAX_DYN");
-    if (P->n_proj < 0 || P->n_proj > 8 || (P->n_proj > 0 && P->n_dyn < 1)) return fail("projectile rows need a dynamic obstacle (n_proj <= 8; they follow the last one)");
+    if (!P) return upr_fail("upr_problem is NULL");
+    if (P->nq != 6 && P->nq != 9) return upr_fail("unsupported chain length nq = " + std::to_string(P->nq) + " (kernels are instantiated for 6 and 9 joints)");
+    if (P->nb < 1 || P->nb > UPR_MAX_BODIES) return upr_fail("nb out of range");
+    if (P->nc < 1 || P->nc > UPR_MAX_CONTACTS) return upr_fail("nc out of range");
+    if (P->nf != 1 && P->nf != 3) return upr_fail("nf must be 1 or 3");
+    if (P->N < 1 || P->N > 1000) return upr_fail("N out of range");
+    if (!(P->dt > 0)) return upr_fail("dt must be positive");
+    if (P->n_way < 1 || P->n_way > UPR_MAX_WAYPOINTS) return upr_fail("n_way out of range");
+    for (int i = 0; i < 6; ++i) if (!(P->Wee[i] >= 0)) return upr_fail("end-effector weights must be non-negative");
+    if (P->n_sph < 0 || P->n_sph > UPR_MAX_SPHERES) return upr_fail("n_sph out of range");
+    if (P->n_pairs < 0 || P->n_pairs > UPR_MAX_PAIRS) return upr_fail("n_pairs out of range");
+    if (P->n_dyn < 0 || P->n_dyn > UPR_MAX_DYN) return upr_fail("n_dyn must be in 0 .. UPR_MAX_DYN");
+    if (P->n_proj < 0 || P->n_proj > 8 || (P->n_proj > 0 && P->n_dyn < 1)) return upr_fail("projectile rows need a dynamic obstacle (n_proj <= 8; they follow the last one)");
     if (P->soft_state_box || P->soft_input_box || P->soft_poly) {
-        if (!(P->soft_L2_lower >= 0) || !(P->soft_L2_upper >= 0) || !(P->soft_L1_lower >= 0) || !(P->soft_L1_upper >= 0)) return fail("slack penalties must be non-negative");
-        if (!(P->soft_L2_lower + P->soft_L1_lower > 0) || !(P->soft_L2_upper + P->soft_L1_upper > 0)) return fail("softened rows need a positive L1 or L2 penalty");
+        if (!(P->soft_L2_lower >= 0) || !(P->soft_L2_upper >= 0) || !(P->soft_L1_lower >= 0) || !(P->soft_L1_upper >= 0)) return upr_fail("slack penalties must be non-negative");
+        if (!(P->soft_L2_lower + P->soft_L1_lower > 0) || !(P->soft_L2_upper + P->soft_L1_upper > 0)) return upr_fail("softened rows need a positive L1 or L2 penalty");
     }
     if (P->soft_eq && (!(P->soft_L2_lower > 0) || P->soft_L2_lower != P->soft_L2_upper || P->soft_L1_lower != 0 || P->soft_L1_upper != 0))
-        return fail("a softened object-dynamics equality needs equal positive L2 penalties and zero L1 penalties (the slack pair is eliminated to a quadratic penalty)");
-    for (int i = 0; i < P->n_proj; ++i) if (P->proj_sph[i] < 0 || P->proj_sph[i] >= P->n_sph || !(P->proj_dist[i] > 0)) return fail("projectile row out of range");
-    for (int i = 0; i < P->n_sph; ++i) if (P->sph_frame[i] > P->nq || (P->sph_frame[i] <= -2 && -2 - P->sph_frame[i] >= P->n_dyn)) return fail("sph_frame out of range");
+        return upr_fail("a softened object-dynamics equality needs equal positive L2 penalties and zero L1 penalties (the slack pair is eliminated to a quadratic penalty)");
+    for (int i = 0; i < P->n_proj; ++i) if (P->proj_sph[i] < 0 || P->proj_sph[i] >= P->n_sph || !(P->proj_dist[i] > 0)) return upr_fail("projectile row out of range");
+    for (int i = 0; i < P->n_sph; ++i) if (P->sph_frame[i] > P->nq || (P->sph_frame[i] <= -2 && -2 - P->sph_frame[i] >= P->n_dyn)) return upr_fail("sph_frame out of range");
     for (int i = 0; i < P->n_pairs; ++i)
-        if (P->pair_a[i] < 0 || P->pair_a[i] >= P->n_sph || P->pair_b[i] < -1 || P->pair_b[i] >= P->n_sph || P->pair_a[i] == P->pair_b[i]) return fail("collision pair out of range");
+        if (P->pair_a[i] < 0 || P->pair_a[i] >= P->n_sph || P->pair_b[i] < -1 || P->pair_b[i] >= P->n_sph || P->pair_a[i] == P->pair_b[i]) return upr_fail("collision pair out of range");
     if (P->ee_box) for (int i = 0; i < 3; ++i)
         if (!std::isfinite(P->ee_box_lower[i]) || !std::isfinite(P->ee_box_upper[i]) || P->ee_box_lower[i] > P->ee_box_upper[i])
-            return fail("end-effector box: lower and upper must be finite with lower <= upper");
+            return upr_fail("end-effector box: lower and upper must be finite with lower <= upper");
     for (int i = 0; i < P->nc; ++i) {
-        if (P->contact_body2[i] < 0 || P->contact_body2[i] >= P->nb) return fail("contact_body2 must index a balanced body");
-        if (P->contact_body1[i] >= P->nb) return fail("contact_body1 out of range");
+        if (P->contact_body2[i] < 0 || P->contact_body2[i] >= P->nb) return upr_fail("contact_body2 must index a balanced body");
+        if (P->contact_body1[i] >= P->nb) return upr_fail("contact_body1 out of range");
     }
     return 0;
 }
@@ -462,86 +290,8 @@ int check_problem(const upr_problem* P) {
 int need_device() {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n < 1) return fail("no HIP device available: libupright_mi has no CPU path");
+    if (e != hipSuccess || n < 1) return upr_fail("no HIP device available: libupright_mi has no CPU path");
     return 0;
-}
-
-// the linearisation kernel of the handle (lin_sel) over A.npoints knots
-int launch_linearize(upr_batch* h, const upr_lin_args& A) {
-    const upr_lin_sel& s = h->lin_sel;
-    if (s.too_large) return fail("collision model too large for the linearisation kernel's LDS");
-    if (s.lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute(s.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
-    const int blocks = (A.npoints + s.kpw - 1) / s.kpw;
-    upr_lin_args Ac = A;
-    int kpw = s.kpw, n_sph = h->P.n_sph;
-    void* args[] = {&Ac, &kpw, &n_sph};   // (a kernel takes as many as it declares: upr_linearize_kernel the first alone)
-    UPR_HIP(hipLaunchKernel(s.kern, dim3(blocks), dim3(256), args, s.lds, h->stream));
-    h->lin_blocks_last = blocks;
-    return 0;
-}
-// the instantiation a choice names, at the handle's chain length: the lists of upr_launch_select.h expanded
-template <int NQ>
-const void* lin_kernel(const upr_lin_choice& s) {
-    if (s.kind == 2) return (const void*)upr_linearize2_kernel<NQ>;
-#define X(M, O, R, NP) if (s.mfma == M && s.occ == O && s.ori == R && s.npass == NP) return (const void*)upr_linearize_kernel<NQ, M, O, R, NP>;
-    UPR_LIN_FORMS(X)
-#undef X
-    return nullptr;
-}
-template <int NQ>
-void (*ls_kernel(const upr_ls_choice& s))(upr_ls_args) {
-    // (STAGE is compile-time in the kernel: its staged arrays are LDS pointers, not generic ones)
-#define X(NF, NB, E, O) if (s.nfm == NF && s.nbm == NB && s.exact == E && s.obs == O) \
-        return s.stage ? upr_linesearch_kernel<NQ, 128, NF, NB, E, O, true> : upr_linesearch_kernel<NQ, 128, NF, NB, E, O, false>;
-    UPR_LS_FORMS(X)
-#undef X
-    return nullptr;
-}
-
-typedef int (*upr_qp_launcher)(upr_batch*, const upr_qp_args&);
-
-// generic (runtime-dimension) QP kernel, at the workgroup size upr_qp_generic_nt chose
-template <int NT>
-int launch_qp_generic_nt(upr_batch* h, const upr_qp_args& A) {
-    const upr_qp_lds lay = upr_qp_lds_layout(A.d, NT);
-    const size_t lds = (size_t)lay.total * sizeof(double);
-    if (lds > 160 * 1024) return fail("QP working set exceeds 160 KiB of LDS");
-    if (lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)upr_qp_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(upr_qp_kernel<NT>, dim3(h->B), dim3(NT), lds, h->stream, A);
-    UPR_HIP(hipGetLastError());
-    return 0;
-}
-int launch_qp_generic_bad_nt(upr_batch*, const upr_qp_args&) { return fail("UPR_QP_GENERIC_NT must be 64, 128, 256, 512 or 1024"); }
-upr_qp_launcher qp_generic_launcher(int nt) {
-    switch (nt) {
-        case 64: return launch_qp_generic_nt<64>;
-        case 128: return launch_qp_generic_nt<128>;
-        case 256: return launch_qp_generic_nt<256>;
-        case 512: return launch_qp_generic_nt<512>;
-        case 1024: return launch_qp_generic_nt<1024>;
-        default: return launch_qp_generic_bad_nt;
-    }
-}
-
-template <class D, int NT>
-int launch_qp2_nt(upr_batch* h, const upr_qp_args& A) {
-    const size_t lds = upr_qp2_lds_doubles<D>(A.d.N, NT) * sizeof(double);
-    if (lds > 160 * 1024) return fail("QP working set exceeds 160 KiB of LDS");
-    if (lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)upr_qp2_kernel<D, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((upr_qp2_kernel<D, NT>), dim3(h->B), dim3(NT), lds, h->stream, A);
-    UPR_HIP(hipGetLastError());
-    return 0;
-}
-int launch_qp2_bad_nt(upr_batch*, const upr_qp_args&) { return fail("UPR_QP_NT must be 64, 128 or 256"); }
-template <class D>
-upr_qp_launcher qp2_launcher(int nt) {
-    switch (nt) {
-        case 64: return launch_qp2_nt<D, 64>;
-        case 512:
-        case 128: return launch_qp2_nt<D, 128>;
-        case 256: return launch_qp2_nt<D, 256>;
-        default: return launch_qp2_bad_nt;
-    }
 }
 
 // third-structure ("production") kernel.  The headline shape (nq 9, nb 1, nc 4, nf 3, N 20) at 256 lanes, with and without
@@ -552,12 +302,12 @@ upr_qp_launcher qp2_launcher(int nt) {
 template <class C>
 int launch_qp3_cfg(upr_batch* h, const upr_qp_args& A) {
     const int rc = upr_qp3_launch<C>(h->stream, h->B, A);
-    if (rc == -1) return fail("QP working set exceeds 160 KiB of LDS");
-    if (rc != 0) return fail(std::string("upr_qp3_kernel launch: ") + hipGetErrorString((hipError_t)rc));
+    if (rc == -1) return upr_fail("QP working set exceeds 160 KiB of LDS");
+    if (rc != 0) return upr_fail(std::string("upr_qp3_kernel launch: ") + hipGetErrorString((hipError_t)rc));
     return 0;
 }
 int launch_qp3_bad_nt(upr_batch*, const upr_qp_args&) {
-    return fail("the production QP kernel ships at 256 lanes (UPR_QP_NT = 128 | 512 were A/B instantiations of rounds 1 - 5; UPR_QP3_JIT=2 UPR_JIT_NT=... instantiates one at run time)");
+    return upr_fail("the production QP kernel ships at 256 lanes (UPR_QP_NT = 128 | 512 were A/B instantiations of rounds 1 - 5; UPR_QP3_JIT=2 UPR_JIT_NT=... instantiates one at run time)");
 }
 int launch_qp3_run_time(upr_batch* h, const upr_qp_args& A) {
     const upr_jit_kernel* k = h->qp.jit;
@@ -583,7 +333,7 @@ struct qp_sel_own {
     void operator()(upr_qp2_dims<a, b, c, e>) const {
         typedef upr_qp2_dims<a, b, c, e> D;
         const upr_qp2_ws<D> w(d.N, d.neN);
-        s.launch = qp2_launcher<D>(s.nt);
+        s.launch = qp2_launcher(a, b, c, e, s.nt);
         s.fb.kind = 2; s.fb.k_base = w.store + D::SS_V; s.fb.k_stride = D::SS_STRIDE; s.fb.lji_base = w.store + D::SS_LJI; s.fb.lji_stride = D::SS_STRIDE;
         s.fb.lfi_base = w.pre + D::PR_LFI; s.fb.lfi_stride = D::PR_STRIDE; s.fb.lsi_base = w.pre + D::PR_LSI; s.fb.lsi_stride = D::PR_STRIDE; s.fb.lsi_sb = d.ne;
     }
@@ -632,7 +382,7 @@ bool jit_read(const std::string& path, std::string* out) {
 // the instantiation (tuple; nt lanes: UPR_JIT_NT) that upr_qp_plan asked for
 int jit_get(const int* tuple, int nt, upr_jit_kernel** out) {
     char cfg[128];
-    if (nt != 128 && nt != 256 && nt != 512) return fail("UPR_JIT_NT must be 128, 256 or 512");
+    if (nt != 128 && nt != 256 && nt != 512) return upr_fail("UPR_JIT_NT must be 128, 256 or 512");
     upr_qp3_cfg_text(tuple, nt, cfg, sizeof(cfg));
     int dev = 0;
     UPR_HIP(hipGetDevice(&dev));
@@ -670,7 +420,7 @@ int jit_get(const int* tuple, int nt, upr_jit_kernel** out) {
     auto mix = [&](const std::string& t) { for (unsigned char c : t) { hsh ^= c; hsh *= 1099511628211ull; } hsh ^= 0xff; hsh *= 1099511628211ull; };
     for (const char* f : {"../../include/upright_mi.h", "upr_common.h", "upr_kin.h", "upr_qp.h", "upr_qp2.h", "upr_qp3.h"}) {
         std::string txt;
-        if (!jit_read(dir + "/" + f, &txt)) return fail("run-time instantiation: cannot read " + dir + "/" + f + " (set UPR_CSRC_DIR)");
+        if (!jit_read(dir + "/" + f, &txt)) return upr_fail("run-time instantiation: cannot read " + dir + "/" + f + " (set UPR_CSRC_DIR)");
         mix(txt);
     }
     mix(src);
@@ -707,7 +457,7 @@ int jit_get(const int* tuple, int nt, upr_jit_kernel** out) {
     if (!loaded) {
         fprintf(stderr, "libupright_mi: instantiating the production QP kernel for upr_qp3_cfg<%s> (once per machine: %s)\n", cfg, path.empty() ? "no disk cache" : path.c_str());
         hiprtcProgram prog;
-        if (hiprtcCreateProgram(&prog, src.c_str(), "upr_qp3_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return fail("hiprtcCreateProgram failed");
+        if (hiprtcCreateProgram(&prog, src.c_str(), "upr_qp3_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return upr_fail("hiprtcCreateProgram failed");
         std::vector<const char*> opts;
         for (const std::string& o : optv) opts.push_back(o.c_str());
         const hiprtcResult rc = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
@@ -715,7 +465,7 @@ int jit_get(const int* tuple, int nt, upr_jit_kernel** out) {
             size_t ls = 0; hiprtcGetProgramLogSize(prog, &ls);
             std::string log(ls, 0); if (ls) hiprtcGetProgramLog(prog, &log[0]);
             hiprtcDestroyProgram(&prog);
-            return fail("run-time instantiation of upr_qp3_cfg<" + std::string(cfg) + "> failed: " + log.substr(0, 2000));
+            return upr_fail("run-time instantiation of upr_qp3_cfg<" + std::string(cfg) + "> failed: " + log.substr(0, 2000));
         }
         size_t cs = 0; hiprtcGetCodeSize(prog, &cs);
         code.resize(cs); hiprtcGetCode(prog, &code[0]);
@@ -745,7 +495,7 @@ int jit_get(const int* tuple, int nt, upr_jit_kernel** out) {
     UPR_HIP(hipMemcpy(hi, dp, sizeof(hi), hipMemcpyDeviceToHost));
     k.lds = (size_t)hi[0] * sizeof(double); k.ws = (size_t)hi[1];
     k.fb.kind = 3; k.fb.k_base = hi[2]; k.fb.k_stride = hi[3]; k.fb.lfi_base = hi[4]; k.fb.lfi_stride = hi[5]; k.fb.lsi_base = hi[6]; k.fb.lsi_stride = hi[7]; k.fb.lsi_sb = hi[8];
-    if (k.lds > 160 * 1024) { (void)hipModuleUnload(k.mod); return fail("run-time instantiation: the working set of upr_qp3_cfg<" + std::string(cfg) + "> exceeds 160 KiB of LDS"); }
+    if (k.lds > 160 * 1024) { (void)hipModuleUnload(k.mod); return upr_fail("run-time instantiation: the working set of upr_qp3_cfg<" + std::string(cfg) + "> exceeds 160 KiB of LDS"); }
     if (k.lds > 64 * 1024) UPR_HIP(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
     auto ins = g_jit.emplace(key, k);
     *out = &ins.first->second;
@@ -753,23 +503,6 @@ int jit_get(const int* tuple, int nt, upr_jit_kernel** out) {
 }
 
 int launch_qp(upr_batch* h, const upr_qp_args& A) { return h->qp.launch(h, A); }
-
-// the line-search kernel of the handle (ls_sel), one workgroup per instance
-int launch_linesearch(upr_batch* h, const upr_ls_args& A0) {
-    const upr_ls_sel& s = h->ls_sel;
-    upr_ls_args A = A0;
-    A.n_way = h->P.n_way;
-    static_assert(3 * UPR_MAX_WAYPOINTS <= 128, "a lane per waypoint coordinate");
-    A.stage_full = s.stage ? 1 : 0;
-    if (s.lds > 160 * 1024) return fail("horizon too long for the line-search kernel's LDS");
-    if (s.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)s.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds);
-    // two waves per instance (wave 0: the chain walks of a trial, wave 1: its flat sums): 241 registers, four workgroups per CU by
-    // LDS.  Four waves (more flat lanes, 128 registers a lane for four workgroups per CU: 135 spilled) measured 48 against 33 us.
-    hipLaunchKernelGGL(s.kern, dim3(h->B), dim3(128), s.lds, h->stream, A);
-    h->ls_launched = true;
-    UPR_HIP(hipGetLastError());
-    return 0;
-}
 
 upr_lin_args traj_lin_args(upr_batch* h) {
     upr_lin_args A;
@@ -838,7 +571,7 @@ hipError_t vf_raise_lds_limit() { return hipFuncSetAttribute((const void*)upr_va
 int fb_gather(upr_batch* h) {
     const upr_dims& d = h->d;
     if (!h->fb && dev_alloc(&h->fb, (size_t)h->B * d.N * d.nu * d.nx)) return 1;
-    if (h->qp.fb.kind == 0) return fail("feedback gains: the selected QP kernel names no source for them");
+    if (h->qp.fb.kind == 0) return upr_fail("feedback gains: the selected QP kernel names no source for them");
     if (d.ne <= 6 && d.nfc <= 12) hipLaunchKernelGGL((feedback_kernel<6, 12>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->qp.fb, h->ws, h->lin, h->Df, h->stats, h->fb);
     else hipLaunchKernelGGL((feedback_kernel<6 * UPR_MAX_BODIES, 3 * UPR_MAX_CONTACTS>), dim3(h->B), dim3(256), 0, h->stream, h->dP, d, h->qp.fb, h->ws, h->lin, h->Df, h->stats, h->fb);
     UPR_HIP(hipGetLastError());
@@ -859,7 +592,7 @@ int fb_keep(upr_batch* h) {
 int launch_policy(upr_batch* h, const double* t, const double* x_obs) {
     const upr_dims& d = h->d;
     if (upr_fb_policy_from_factors(h->fbt.state)) {
-        if (h->qp.fb.kind == 0) return fail("feedback gains: the selected QP kernel names no source for them");
+        if (h->qp.fb.kind == 0) return upr_fail("feedback gains: the selected QP kernel names no source for them");
         const size_t lds = sizeof(double) * 2 * d.nu * d.nx;
         if (d.ne <= 6 && d.nfc <= 12) hipLaunchKernelGGL((evaluate_policy_factors_kernel<6, 12>), dim3(h->B), dim3(64), lds, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->qp.fb, h->ws, h->lin, h->Df, h->stats, t, x_obs, h->ev_x, h->ev_u);
         else hipLaunchKernelGGL((evaluate_policy_factors_kernel<6 * UPR_MAX_BODIES, 3 * UPR_MAX_CONTACTS>), dim3(h->B), dim3(64), lds, h->stream, h->dP, d, h->B, h->tprev, h->xs_prev, h->us_prev, h->qp.fb, h->ws, h->lin, h->Df, h->stats, t, x_obs, h->ev_x, h->ev_u);
@@ -935,244 +668,6 @@ int advance_impl(upr_batch* h) {
     return 0;
 }
 
-// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h): the fifteen entry points end here, in balance_call.  An entry fills a REQUEST, which
-// names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
-// go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
-// the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
-// it carves the scratch block region by region, noting with every region what is copied into it before the kernels and out of it
-// after them, and takes the kernel from a table by form and quantity.  Everything is enqueued on the handle's stream behind
-// whatever is in flight and the one synchronisation is the last statement.  The scratch of the calls is one block on the handle
-// that serves nothing else and only grows (bal_buf): a call in the steady state allocates and frees nothing.
-enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
-// the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h) | the
-// path-acceleration margin (upr_pathacc.h) | the retiming of a plan on a speed lattice (upr_retime.h)
-enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5 };
-struct bal_request {
-    const char* who = "";     // the entry, as its messages name it
-    const char* needs = "";   // ... and what they say about its required pointers
-    // the points: the knots of the handle's plan where they lie on the device, or n states x [n][3 nq] on the host
-    bool plan = false; int n = 0; const double* x = nullptr;
-    // the scenarios: parameter blocks on the host, [n_scen][nb][10] for all points or (per) a set of their own for every point /
-    // every instance of the plan.  NULL (plan, n_scen == 1): every instance against its own body parameters
-    int n_scen = 0; const double* params = nullptr; bool per = false;
-    // the friction scale of every scenario (BAL_RHO)
-    int scale = BAL_MU_NONE; const double* mu_scale = nullptr;
-    // the quantity.  The margins (upr_margin.h) run on the same jobs: out is kappa_hi, z the multipliers there, iters the solves
-    // over all evaluations.  Per group every output gains a trailing [n_grp]; mu_base: the scales of the contacts outside the group
-    // ([n_scen][nc]; NULL: ones)
-    int quantity = BAL_RHO; double kappa_max = 0.0; int n_grp = 1; const unsigned* group_mask = nullptr; const double* mu_base = nullptr;
-    // the speed margin: out is speed, four doubles per job; z and y hold two certificates per job, the lower end first; worst /
-    // worst_knot ([B][n_scen][2]; plan) are the window over the knots and the knots that attain it, limit [B] the limit speed
-    double s_max = 0.0; double* limit = nullptr;
-    // the path-acceleration margin: out is accel, four doubles per job, certificates and reductions as the speed margin's; the range
-    // [-d_max, d_max] of sddot at sdot = speed; limit [B][2] the interval of sddot the acceleration boxes allow
-    double d_max = 0.0, speed = 1.0;
-    // the retiming (plan only): the lattice speeds [n_lvl]; start / end a level or -1; common: one time law under all scenarios;
-    // boxes: the velocity and acceleration boxes cut edges.  out is duration, one double per (instance, scenario) or per instance
-    // with common; level [..][N + 1], reach [..][2]; edges [B][n_scen][N][n_lvl] and iters, one per mask row, stay per scenario
-    const double* speeds = nullptr; int n_lvl = 0, start = -1, end = -1; bool common = false, boxes = true;
-    int *level = nullptr, *reach = nullptr; unsigned* edges = nullptr;
-    // the answers on the host; all but the required ones may be NULL.  worst / worst_knot ([B][n_scen][n_grp]; plan, per group): the
-    // largest kappa_hi over the knots of an instance, reduced on the device; out may then be NULL and kappa_hi stays on the device
-    double* out = nullptr;   // rho | kappa_hi
-    double *kappa_lo = nullptr, *z = nullptr, *y = nullptr; int* iters = nullptr; double* worst = nullptr; int* worst_knot = nullptr;
-};
-long long bal_points(const upr_batch* h, const bal_request& r) { return r.plan ? (long long)h->B * (h->d.N + 1) : r.n; }
-size_t bal_param_sets(const upr_batch* h, const bal_request& r) { return (size_t)(r.per ? (r.plan ? h->B : r.n) : 1) * r.n_scen; }
-
-size_t bal_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-// the next region of a scratch block of `total` bytes so far: its offset (a region that is not wanted takes no room)
-size_t bal_take(size_t& total, size_t bytes, bool wanted) { const size_t o = total; total += wanted ? bal_up(bytes) : 0; return o; }
-int balance_scratch(upr_batch* h, size_t bytes) {
-    if (bytes <= h->bal_cap) return 0;
-    if (h->bal_buf) { UPR_HIP(hipFree(h->bal_buf)); h->bal_buf = nullptr; h->bal_cap = 0; }
-    UPR_HIP(hipMalloc(&h->bal_buf, bytes));
-    h->bal_cap = bytes;
-    return 0;
-}
-int balance_check_groups(const upr_batch* h, int n_grp, const unsigned* group_mask) {
-    if (n_grp < 1 || n_grp > 65535) return fail("friction margin of contact groups: n_grp must be in 1 .. 65535");
-    if (!group_mask) return fail("friction margin of contact groups: group_mask must not be NULL");
-    const int nc = h->d.nc;
-    for (int g = 0; g < n_grp; ++g) {
-        if (group_mask[g] == 0u) return fail("friction margin of contact groups: group " + std::to_string(g) + " has an empty mask");
-        if (nc < 32 && (group_mask[g] >> nc) != 0u)
-            return fail("friction margin of contact groups: group " + std::to_string(g) + " has a mask bit >= nc = " + std::to_string(nc));
-    }
-    return 0;
-}
-int balance_check_scales(const double* v, size_t count, const char* what) {
-    if (v) for (size_t i = 0; i < count; ++i)
-        if (!(v[i] >= 0) || !std::isfinite(v[i])) return fail(std::string("balance check: every ") + what + " must be finite and >= 0");
-    return 0;
-}
-// 0: a request to launch; 1: refused (upr_last_error says why); 2: no points, nothing to do
-int balance_validate(const upr_batch* h, const bal_request& r) {
-    const upr_dims& d = h->d;
-    auto refuse = [&](const char* why) { return fail(std::string(r.who) + ": " + why); };
-    const bool margin = r.quantity == BAL_MARGIN || r.quantity == BAL_MARGIN_GROUPS;
-    if (margin && (!(r.kappa_max > 0) || !std::isfinite(r.kappa_max))) return fail("friction margin: kappa_max must be finite and > 0");
-    if (r.quantity == BAL_SPEED && (!(r.s_max > 1) || !std::isfinite(r.s_max))) return fail("speed margin: s_max must be finite and > 1");
-    if (r.quantity == BAL_PATHACC && (!(r.d_max > 0) || !std::isfinite(r.d_max) || !(r.speed >= 0) || !std::isfinite(r.speed)))
-        return fail("path-acceleration margin: d_max must be finite and > 0, speed finite and >= 0");
-    if (r.quantity == BAL_MARGIN_GROUPS && balance_check_groups(h, r.n_grp, r.group_mask)) return 1;
-    if (!r.plan && r.n <= 0) return 2;
-    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst && !r.level)) return refuse(r.needs);
-    if (r.plan && !r.params) {
-        if (r.n_scen != 1) return refuse("params == NULL needs n_scen == 1 (every instance's own body parameters)");
-    } else if (r.n_scen < 1) return refuse("n_scen must be >= 1");
-    if (r.params) for (size_t i = 0, e = bal_param_sets(h, r) * d.nb; i < e; ++i)
-        if (!(r.params[10 * i] > 0) || !std::isfinite(r.params[10 * i])) return fail("balance check: every body of every scenario needs a positive finite mass");
-    if (balance_check_scales(r.mu_scale, (size_t)r.n_scen * (r.scale == BAL_MU_CONTACT ? d.nc : 1), "mu_scale")) return 1;
-    if (balance_check_scales(r.mu_base, (size_t)r.n_scen * d.nc, "mu_base")) return 1;
-    const long long n = bal_points(h, r);
-    if (n > (1ll << 31) - 64 || n * r.n_scen * r.n_grp > (1ll << 36)) return fail("balance check: too many points");
-    if (r.quantity == BAL_RETIME) {
-        bool ok = r.speeds && r.n_lvl >= 1 && r.n_lvl <= UPR_RET_MAX_LEVELS;
-        for (int m = 0; ok && m < r.n_lvl; ++m) ok = std::isfinite(r.speeds[m]) && r.speeds[m] >= 0 && (m == 0 || r.speeds[m] > r.speeds[m - 1]);
-        if (!ok) return fail("retime: speeds must be 1 .. 32 finite values >= 0 in strictly increasing order");
-        if (r.start < -1 || r.start >= r.n_lvl || r.end < -1 || r.end >= r.n_lvl) return fail("retime: start and end must be -1 or a level index");
-        if (n * r.n_scen * r.n_lvl > (1ll << 36)) return fail("balance check: too many points");   // (the jobs: a mask row each)
-    }
-    return 0;
-}
-
-// form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
-// group, the speed margin, the path-acceleration margin, the edge masks of the retiming.  Every kernel takes (its record, upr_bal_dims,
-// long long jobs); the record is upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the groups, upr_spd_args for the
-// speed margin, upr_pac_args for the path-acceleration margin and upr_ret_args for the retiming.
-const void* const bal_kernels[2][8] = {
-    /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
-                    (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel,
-                    (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel},
-    /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
-                    (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel,
-                    (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel}};
-struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
-
-int balance_launch(upr_batch* h, const bal_request& r) {
-    const upr_dims& d = h->d;
-    upr_bal_dims L = h->bal.L;
-    const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, speed = r.quantity == BAL_SPEED || pathacc;   // (speed: the four-double layout)
-    const bool retime = r.quantity == BAL_RETIME;
-    const bool margin = r.quantity != BAL_RHO && !speed && !retime, groups = r.quantity == BAL_MARGIN_GROUPS;
-    // (the retiming: a job is a mask row, (instance, scenario, segment, level); nplans outputs of the path kernel)
-    const long long n = bal_points(h, r), njobs = retime ? (long long)h->B * r.n_scen * d.N * r.n_lvl : n * r.n_scen, ng = r.n_grp, nout = njobs * ng;
-    const long long nplans = retime ? (long long)h->B * (r.common ? 1 : r.n_scen) : 0;
-    const bool want_worst = r.worst || r.worst_knot;
-    const long long nworst = want_worst ? (long long)h->B * r.n_scen * (speed ? 2 : ng) : 0;
-    const size_t per_out = speed ? 4 : 1, ends = speed ? 2 : 1;   // doubles of `out` and certificates per job
-    const double* scale_host = groups ? r.mu_base : r.mu_scale;
-    const size_t scale_count = (size_t)r.n_scen * ((groups || r.scale == BAL_MU_CONTACT) ? d.nc : 1);
-    // the scratch block, region by region, with what goes into a region before the kernels (from) and out of it after them (to)
-    bal_copy up[4], down[8];
-    int nup = 0, ndown = 0; size_t total = 0;
-    auto region = [&](size_t bytes, bool wanted, const void* from, void* to) {
-        const size_t o = bal_take(total, bytes, wanted);
-        if (wanted && from) up[nup++] = {o, const_cast<void*>(from), bytes};
-        if (wanted && to) down[ndown++] = {o, to, bytes};
-        return o;
-    };
-    const size_t o_st = region(sizeof(double) * n * UPR_BAL_ST, true, nullptr, nullptr);
-    const size_t o_rho = region(sizeof(double) * (retime ? nplans : nout * per_out), true, nullptr, r.out);
-    const size_t o_z = region(sizeof(double) * nout * ends * L.ncol, r.z != nullptr, nullptr, r.z);
-    const size_t o_it = region(sizeof(int) * nout, r.iters != nullptr, nullptr, r.iters);
-    const size_t o_par = region(sizeof(double) * bal_param_sets(h, r) * d.nb * 10, r.params != nullptr, r.params, nullptr);
-    const size_t o_x = region(sizeof(double) * n * d.nx, !r.plan, r.x, nullptr);
-    const size_t o_mu = region(sizeof(double) * scale_count, scale_host != nullptr, scale_host, nullptr);
-    const size_t o_lo = region(sizeof(double) * nout, r.kappa_lo != nullptr, nullptr, r.kappa_lo);
-    const size_t o_y = region(sizeof(double) * nout * ends * L.m, r.y != nullptr, nullptr, r.y);
-    const size_t o_gm = region(sizeof(unsigned) * ng, groups, r.group_mask, nullptr);
-    const size_t o_w = region(sizeof(double) * nworst, want_worst, nullptr, r.worst);
-    const size_t o_wk = region(sizeof(int) * nworst, want_worst, nullptr, r.worst_knot);
-    const size_t o_lim = region(sizeof(double) * h->B * (pathacc ? 2 : 1), r.limit != nullptr, nullptr, r.limit);
-    const size_t o_vee = region(sizeof(double) * n * 3, pathacc || retime, nullptr, nullptr);
-    const size_t o_spd = region(sizeof(double) * r.n_lvl, retime, r.speeds, nullptr);
-    const size_t o_edg = region(sizeof(unsigned) * nout, retime, nullptr, r.edges);
-    const size_t o_arg = region((size_t)nplans * d.N * r.n_lvl, retime, nullptr, nullptr);
-    const size_t o_lvl = region(sizeof(int) * nplans * (d.N + 1), retime, nullptr, r.level);
-    const size_t o_rch = region(sizeof(int) * nplans * 2, retime && r.reach, nullptr, r.reach);
-    if (balance_scratch(h, total)) return 1;
-    char* base = (char*)h->bal_buf;
-    for (int i = 0; i < nup; ++i) UPR_HIP(hipMemcpyAsync(base + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, h->stream));
-    if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
-    UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
-    const double* dx = r.plan ? h->xs : (const double*)(base + o_x);
-    double *dst = (double*)(base + o_st), *drho = (double*)(base + o_rho);
-    const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
-    if ((pathacc || retime) && h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_vee_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
-    else if (pathacc || retime) hipLaunchKernelGGL(upr_bal_state_vee_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
-    else if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
-    else hipLaunchKernelGGL(upr_bal_state_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
-    UPR_HIP(hipGetLastError());
-    upr_bal_args A;
-    A.P = h->dP; A.n = (int)n; A.n_scen = r.n_scen; A.st = dst; A.eq_scale = d.eq_scale;
-    A.params = r.params ? (const double*)(base + o_par) : h->body_params;
-    A.pdiv = r.plan ? ((r.per || !r.params) ? d.N + 1 : 0) : (r.per ? 1 : 0);   // points that share a parameter set
-    A.rho = drho; A.z = r.z ? (double*)(base + o_z) : nullptr; A.iters = r.iters ? (int*)(base + o_it) : nullptr;
-    A.mu_scale = r.mu_scale ? (const double*)(base + o_mu) : nullptr;
-    upr_mar_args M;
-    if (margin) {
-        M.J = A; M.J.rho = nullptr; M.kappa_max = r.kappa_max; M.kappa_hi = drho;
-        M.kappa_lo = r.kappa_lo ? (double*)(base + o_lo) : nullptr; M.y = r.y ? (double*)(base + o_y) : nullptr;
-    }
-    upr_spd_args S;
-    if (speed && !pathacc) { S.J = A; S.J.rho = nullptr; S.s_max = r.s_max; S.speed = drho; S.y = r.y ? (double*)(base + o_y) : nullptr; }
-    upr_pac_args C;
-    if (pathacc) {
-        C.J = A; C.J.rho = nullptr; C.d_max = r.d_max; C.speed = r.speed; C.vee = (const double*)(base + o_vee); C.accel = drho;
-        C.y = r.y ? (double*)(base + o_y) : nullptr;
-    }
-    upr_ret_args T;
-    if (retime) {
-        T.J = A; T.J.rho = nullptr; T.vee = (const double*)(base + o_vee); T.xs = dx; T.speeds = (const double*)(base + o_spd); T.M = r.n_lvl;
-        T.nk = d.N + 1; T.nx = d.nx; T.boxes = r.boxes ? 1 : 0; T.h = h->P.dt; T.edges = (unsigned*)(base + o_edg);
-    }
-    upr_grp_args X;
-    if (groups) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = r.mu_base ? (const double*)(base + o_mu) : nullptr; }
-    // lane form: 64 jobs per workgroup, the groups on the y axis.  Wave form: a workgroup is one wave and the jobs (for the groups:
-    // job x group) are dealt round robin to a grid that fills the device a few times over (its LDS, at most 26.4 KB, lets six of
-    // the largest shape share a CU inside the 160 KiB)
-    long long count = (wave && groups) ? nout : njobs;
-    const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
-    void* args[] = {retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
-    UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
-    if (retime) {
-        upr_ret_path_args Q;
-        Q.edges = T.edges; Q.speeds = T.speeds; Q.M = r.n_lvl; Q.nk = d.N + 1; Q.n_scen = r.n_scen; Q.common = r.common ? 1 : 0; Q.start = r.start; Q.end = r.end;
-        Q.h = h->P.dt; Q.arg = (unsigned char*)(base + o_arg); Q.duration = drho; Q.level = (int*)(base + o_lvl); Q.reach = r.reach ? (int*)(base + o_rch) : nullptr;
-        hipLaunchKernelGGL(upr_bal_retime_path_kernel, dim3((unsigned)(nplans < 16384 ? nplans : 16384)), dim3(64), 0, h->stream, Q, nplans);
-        UPR_HIP(hipGetLastError());
-    } else if (pathacc && (want_worst || r.limit)) {
-        const long long lanes = nworst + (r.limit ? h->B : 0);
-        hipLaunchKernelGGL(upr_bal_pathacc_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
-                           d.N + 1, r.n_scen, nworst, h->B, d.nx, r.speed, (const double*)h->xs, (double*)(base + o_w),
-                           r.worst_knot ? (int*)(base + o_wk) : nullptr, r.limit ? (double*)(base + o_lim) : nullptr);
-        UPR_HIP(hipGetLastError());
-    } else if (speed && (want_worst || r.limit)) {
-        const long long lanes = nworst + (r.limit ? h->B : 0);
-        hipLaunchKernelGGL(upr_bal_speed_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
-                           d.N + 1, r.n_scen, nworst, h->B, d.nx, d.nu, (const double*)h->xs, (const double*)h->us, (double*)(base + o_w),
-                           r.worst_knot ? (int*)(base + o_wk) : nullptr, r.limit ? (double*)(base + o_lim) : nullptr);
-        UPR_HIP(hipGetLastError());
-    } else if (want_worst) {
-        hipLaunchKernelGGL(upr_bal_margin_worst_kernel, dim3((unsigned)((nworst + 63) / 64)), dim3(64), 0, h->stream, (const double*)drho, d.N + 1,
-                           (long long)r.n_scen * ng, nworst, (double*)(base + o_w), r.worst_knot ? (int*)(base + o_wk) : nullptr);
-        UPR_HIP(hipGetLastError());
-    }
-    UPR_HIP(hipEventRecord(h->bal_ev[1], h->stream));
-    for (int i = 0; i < ndown; ++i) UPR_HIP(hipMemcpyAsync(down[i].host, base + down[i].off, down[i].bytes, hipMemcpyDeviceToHost, h->stream));
-    UPR_HIP(hipStreamSynchronize(h->stream));
-    float ms = 0.0f;
-    UPR_HIP(hipEventElapsedTime(&ms, h->bal_ev[0], h->bal_ev[1]));
-    h->bal_ms = ms;
-    return 0;
-}
-int balance_call(upr_batch* h, const bal_request& r) {
-    if (const int v = balance_validate(h, r)) return v == 1;
-    return balance_launch(h, r);
-}
-
 // ---- what several entries share -------------------------------------------------------------------------------------------
 // the time of every instance: t[B], or one time for all (t_stride == 0)
 void instance_times(int B, const double* t, int t_stride, double* out) {
@@ -1201,7 +696,7 @@ int snapshot_put_back(upr_batch* h, const upr_stats_snapshot& s) {
 struct point_upload {
     DevBuf<int> inst; DevBuf<double> t;
     int up(const upr_batch* h, int n, const int* hinst, const double* ht) {
-        for (int i = 0; i < n; ++i) if (hinst[i] < 0 || hinst[i] >= h->B) return fail("instance index out of range");
+        for (int i = 0; i < n; ++i) if (hinst[i] < 0 || hinst[i] >= h->B) return upr_fail("instance index out of range");
         if (inst.alloc(n) || t.alloc(n)) return 1;
         UPR_HIP(hipMemcpy(inst, hinst, sizeof(int) * n, hipMemcpyHostToDevice));
         UPR_HIP(hipMemcpy(t, ht, sizeof(double) * n, hipMemcpyHostToDevice));
@@ -1223,7 +718,7 @@ int upr_device_available(void) {
 int upr_core_object_dynamics(const upr_problem* P, const double* body_params, int n, const double* forces, const double* C,
                              const double* w, const double* al, const double* a, double* out) {
     if (need_device()) return 1;
-    if (!P || P->nb < 1 || P->nb > UPR_MAX_BODIES || P->nc < 0 || P->nc > UPR_MAX_CONTACTS) return fail("bad problem dims");
+    if (!P || P->nb < 1 || P->nb > UPR_MAX_BODIES || P->nc < 0 || P->nc > UPR_MAX_CONTACTS) return upr_fail("bad problem dims");
     if (n <= 0) return 0;
     const int nfc = P->nf * P->nc, nb = P->nb;
     DevBuf<upr_problem> dP; DevBuf<double> dbp, df, dC, dw, dal, da, dout;
@@ -1244,7 +739,7 @@ int upr_core_object_dynamics(const upr_problem* P, const double* body_params, in
 
 int upr_core_friction_rows(const upr_problem* P, int n, const double* forces, double* out) {
     if (need_device()) return 1;
-    if (!P || P->nc < 1 || P->nc > UPR_MAX_CONTACTS) return fail("bad problem dims");
+    if (!P || P->nc < 1 || P->nc > UPR_MAX_CONTACTS) return upr_fail("bad problem dims");
     if (n <= 0) return 0;
     DevBuf<upr_problem> dP; DevBuf<double> df, dout;
     if (dP.alloc(1) || df.alloc((size_t)n * 3 * P->nc) || dout.alloc((size_t)n * 5 * P->nc)) return 1;
@@ -1258,15 +753,15 @@ int upr_core_friction_rows(const upr_problem* P, int n, const double* forces, do
 
 upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_params, const double* way_p) {
     if (check_problem(P)) return nullptr;
-    if (B < 1) { fail("B must be >= 1"); return nullptr; }
+    if (B < 1) { upr_fail("B must be >= 1"); return nullptr; }
     if (need_device()) return nullptr;
     upr_batch* h = new upr_batch();
-    if (hipGetDevice(&h->device) != hipSuccess) { fail("hipGetDevice failed"); delete h; return nullptr; }
+    if (hipGetDevice(&h->device) != hipSuccess) { upr_fail("hipGetDevice failed"); delete h; return nullptr; }
     h->P = *P; h->d = upr_make_dims(P); h->B = B;
     h->nxf = (int)upr_iface_width(h->d.nx, P->n_dyn);
     h->hdyn0.assign((size_t)B * upr_iface_dyn_width(P->n_dyn), 0.0); h->hdyn_prev = h->hdyn0;
     const upr_dims& d = h->d;
-    if (d.nx > UPR_LPK) { fail("nx exceeds the 32 tangent lanes of the linearisation kernel"); delete h; return nullptr; }
+    if (d.nx > UPR_LPK) { upr_fail("nx exceeds the 32 tangent lanes of the linearisation kernel"); delete h; return nullptr; }
     {   // the QP kernel of this handle (upr_qp_select.h): planned from the problem and the knobs, a run-time instantiation made where the
         // plan asks for one, then resolved into the record every later site reads
         upr_qp_knobs k;
@@ -1288,30 +783,12 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
         qp_resolve(s, *P, d);
         h->d.ws_stride = s.ws_stride;
     }
-    {   // ... and its linearisation and line-search kernels (upr_launch_select.h)
-        upr_lin_knobs kl; upr_ls_knobs ks;
-        if (const char* e = getenv("UPR_LIN_MFMA")) kl.mfma = atoi(e) != 0;
-        if (const char* e = getenv("UPR_LIN2")) kl.lin2 = atoi(e) != 0;
-        if (const char* e = getenv("UPR_LIN_OCC")) kl.occ = atoi(e);
-        if (const char* e = getenv("UPR_LIN_ROW_PASSES")) kl.row_passes = atoi(e);
-        if (const char* e = getenv("UPR_LS_STAGE_FULL")) ks.stage_full = atoi(e);
-        static_cast<upr_lin_choice&>(h->lin_sel) = upr_lin_plan(*P, d, kl);
-        static_cast<upr_ls_choice&>(h->ls_sel) = upr_ls_plan(*P, d, ks);
-        h->lin_sel.kern = (P->nq == 6) ? lin_kernel<6>(h->lin_sel) : lin_kernel<9>(h->lin_sel);
-        h->ls_sel.kern = (P->nq == 6) ? ls_kernel<6>(h->ls_sel) : ls_kernel<9>(h->ls_sel);
-        upr_ls_name(h->ls_sel, h->ls_sel.name, sizeof(h->ls_sel.name));
-        if (!h->lin_sel.kern || !h->ls_sel.kern) { fail("the planned linearisation / line-search form is not an instantiation of upr_launch_select.h's lists"); delete h; return nullptr; }
-    }
+    if (upr_launch_resolve(h)) { delete h; return nullptr; }   // ... and its linearisation and line-search kernels (upr_api_launch.hip)
     if (const char* e = getenv("UPR_QP_ORDER")) h->order_on = atoi(e) != 0;
-    {   // ... and the form of its balance family (UPR_BAL_FORM=0: the wave form for the one-body shapes too; tests)
-        const char* e = getenv("UPR_BAL_FORM");
-        h->bal.L = upr_bal_layout(d.nb, d.nc, d.nf);
-        h->bal.lds = (size_t)h->bal.L.total * sizeof(double);
-        h->bal.form = (upr_bal_lane_form(d.nb) && !(e && atoi(e) == 0)) ? BAL_LANE : BAL_WAVE;
-    }
+    upr_bal_resolve(h);   // ... and the form of its balance family (upr_api_balance.hip)
     auto bad = [&]() { upr_batch_destroy(h); return (upr_batch*)nullptr; };
-    if (hipStreamCreate(&h->stream) != hipSuccess) { fail("hipStreamCreate failed"); return bad(); }
-    if (hipMalloc((void**)&h->dP, sizeof(upr_problem)) != hipSuccess) { fail("hipMalloc failed"); return bad(); }
+    if (hipStreamCreate(&h->stream) != hipSuccess) { upr_fail("hipStreamCreate failed"); return bad(); }
+    if (hipMalloc((void**)&h->dP, sizeof(upr_problem)) != hipSuccess) { upr_fail("hipMalloc failed"); return bad(); }
     hipMemcpy(h->dP, P, sizeof(upr_problem), hipMemcpyHostToDevice);
     const size_t n1 = d.N + 1;
     if (dev_alloc(&h->body_params, (size_t)B * d.nb * 10) || dev_alloc(&h->way_p, (size_t)B * P->n_way * 3) || dev_alloc(&h->way_q, (size_t)B * P->n_way * 4) ||
@@ -1349,7 +826,7 @@ upr_batch* upr_batch_create(const upr_problem* P, int B, const double* body_para
         }
     }
     hipMemcpy(h->Df, h->hDf.data(), sizeof(double) * h->hDf.size(), hipMemcpyHostToDevice);
-    if (hipDeviceSynchronize() != hipSuccess) { fail("device synchronisation failed in create"); return bad(); }
+    if (hipDeviceSynchronize() != hipSuccess) { upr_fail("device synchronisation failed in create"); return bad(); }
     return h;
 }
 
@@ -1383,11 +860,11 @@ int upr_batch_reset(upr_batch* h, const double* way_p) {
 
 int upr_batch_set_target_orientations(upr_batch* h, const double* way_q) {
     UPR_ENTER(h);
-    if (!way_q) return fail("upr_batch_set_target_orientations: way_q is NULL");
+    if (!way_q) return upr_fail("upr_batch_set_target_orientations: way_q is NULL");
     std::vector<double> q(way_q, way_q + (size_t)h->B * h->P.n_way * 4);
     for (size_t i = 0; i < q.size(); i += 4) {   // unit quaternions (the reference builds Quatd from the target's coefficients)
         const double n = std::sqrt(q[i] * q[i] + q[i + 1] * q[i + 1] + q[i + 2] * q[i + 2] + q[i + 3] * q[i + 3]);
-        if (!(n > 0)) return fail("upr_batch_set_target_orientations: zero quaternion");
+        if (!(n > 0)) return upr_fail("upr_batch_set_target_orientations: zero quaternion");
         for (int c = 0; c < 4; ++c) q[i + c] /= n;
     }
     UPR_HIP(hipMemcpyAsync(h->way_q, q.data(), sizeof(double) * q.size(), hipMemcpyHostToDevice, h->stream));
@@ -1417,7 +894,7 @@ static int set_guess_core(upr_batch* h, const double* xs, const double* us) {
 
 int upr_batch_set_sqp_iterations(upr_batch* h, int n) {
     UPR_ENTER(h);
-    if (n < 0 || n > 1000) return fail("upr_batch_set_sqp_iterations: n out of range");
+    if (n < 0 || n > 1000) return upr_fail("upr_batch_set_sqp_iterations: n out of range");
     h->sqp_iters_next = n;
     return 0;
 }
@@ -1457,7 +934,7 @@ static int get_solution_core(upr_batch* h, double* ts, double* xs, double* us) {
 
 // the plan at the times t: evaluate, or (policy) evaluate_policy at the observed robot states x_obs[B][nx]
 static int evaluate_core(upr_batch* h, const double* t, int t_stride, bool policy, const double* x_obs, double* x_out, double* u_out) {
-    if (policy && !h->fb_on) return fail("upr_batch_evaluate_policy: the batch was created with use_feedback_policy = 0");
+    if (policy && !h->fb_on) return upr_fail("upr_batch_evaluate_policy: the batch was created with use_feedback_policy = 0");
     const upr_dims& d = h->d;
     if (eval_scratch(h)) return 1;
     std::vector<double> tt(h->B);
@@ -1475,7 +952,7 @@ static int evaluate_core(upr_batch* h, const double* t, int t_stride, bool polic
 }
 
 static int get_feedback_core(upr_batch* h, double* K) {
-    if (!h->fb_on) return fail("upr_batch_get_feedback: the batch was created with use_feedback_policy = 0");
+    if (!h->fb_on) return upr_fail("upr_batch_get_feedback: the batch was created with use_feedback_policy = 0");
     const upr_dims& d = h->d;
     if (fb_keep(h)) return 1;   // the first request after an advance gathers the array; later ones only copy
     if (!h->fb && dev_alloc(&h->fb, (size_t)h->B * d.N * d.nu * d.nx)) return 1;   // (no solve yet: zeros)
@@ -1506,7 +983,7 @@ int upr_batch_hold_stats(upr_batch* h, int restore) {
     UPR_ENTER(h);
     UPR_HIP(hipStreamSynchronize(h->stream));
     if (!restore) return snapshot_take(h, h->held);
-    if (h->held.stats.empty()) return fail("upr_batch_hold_stats: nothing held on this handle");
+    if (h->held.stats.empty()) return upr_fail("upr_batch_hold_stats: nothing held on this handle");
     if (fb_keep(h)) return 1;   // (the QP status the gains' readers consult is overwritten below)
     UPR_HIP(hipStreamSynchronize(h->stream));
     if (snapshot_put_back(h, h->held)) return 1;
@@ -1587,7 +1064,7 @@ static int state_rows_impl(upr_batch* h, int n, const int* inst, const double* t
 int upr_batch_obstacle_rows(upr_batch* h, int n, const double* x, double* dd, double* dq) {
     UPR_ENTER(h);
     const upr_dims& d = h->d;
-    if (d.nsr == 0) return fail("upr_batch_obstacle_rows: the problem has no collision pairs / projectile rows");
+    if (d.nsr == 0) return upr_fail("upr_batch_obstacle_rows: the problem has no collision pairs / projectile rows");
     if (n <= 0) return 0;
     std::vector<int> inst(n, 0);
     std::vector<double> t(n, 0.0);
@@ -1597,14 +1074,14 @@ int upr_batch_obstacle_rows(upr_batch* h, int n, const double* x, double* dd, do
 int upr_batch_state_rows(upr_batch* h, int n, const int* inst, const double* t, const double* x, double* dd, double* dq) {
     UPR_ENTER(h);
     const upr_dims& d = h->d;
-    if (d.no == 0) return fail("upr_batch_state_rows: the problem has no state rows");
+    if (d.no == 0) return upr_fail("upr_batch_state_rows: the problem has no state rows");
     if (n <= 0) return 0;
     return state_rows_impl(h, n, inst, t, x, d.no, dd, dq);   // (inst is checked where it is uploaded: point_upload)
 }
 
 int upr_batch_eq_input_jacobian(upr_batch* h, int inst, double* gu) {
     UPR_ENTER(h);
-    if (inst < 0 || inst >= h->B) return fail("instance index out of range");
+    if (inst < 0 || inst >= h->B) return upr_fail("instance index out of range");
     const upr_dims& d = h->d;
     for (int r = 0; r < d.ne; ++r) {
         for (int j = 0; j < d.nq; ++j) gu[(size_t)r * d.nu + j] = 0.0;
@@ -1691,7 +1168,7 @@ static int qp_kkt_core(upr_batch* h, double* dxs, double* dus, double* pi, doubl
  * lam (1 where a slot is not a row of the knot): lam / t are the barrier weights of the last interior-point iterate. */
 int upr_batch_qp_slacks(upr_batch* h, double* t) {
     UPR_ENTER(h);
-    if (h->kkt_slack.empty()) return fail("upr_batch_qp_slacks: no upr_batch_qp_kkt call on this handle yet");
+    if (h->kkt_slack.empty()) return upr_fail("upr_batch_qp_slacks: no upr_batch_qp_kkt call on this handle yet");
     if (t) std::memcpy(t, h->kkt_slack.data(), sizeof(double) * h->kkt_slack.size());
     return 0;
 }
@@ -1702,7 +1179,7 @@ int upr_batch_qp_slacks(upr_batch* h, double* t) {
  * Any pointer may be NULL. */
 int upr_batch_qp_slack_pairs(upr_batch* h, double* sigma, double* tau, double* gam) {
     UPR_ENTER(h);
-    if (h->kkt_pairs.empty()) return fail("upr_batch_qp_slack_pairs: no upr_batch_qp_kkt call on this handle yet");
+    if (h->kkt_pairs.empty()) return upr_fail("upr_batch_qp_slack_pairs: no upr_batch_qp_kkt call on this handle yet");
     const size_t n = h->kkt_pairs.size() / 3;
     double* out[3] = {sigma, tau, gam};
     for (int q = 0; q < 3; ++q) if (out[q]) std::memcpy(out[q], h->kkt_pairs.data() + q * n, sizeof(double) * n);
@@ -1712,11 +1189,11 @@ int upr_batch_qp_slack_pairs(upr_batch* h, double* sigma, double* tau, double* g
 /* ---- value function of the last QP, batched (upr_value.h) ---- */
 int upr_batch_value_function_update_interface(upr_batch* h) {
     UPR_ENTER(h);
-    if (!h->has_prev && !h->guess_set) return fail("upr_batch_value_function_update: no plan on this handle yet (advance or set a guess first)");
+    if (!h->has_prev && !h->guess_set) return upr_fail("upr_batch_value_function_update: no plan on this handle yet (advance or set a guess first)");
     const upr_dims& d = h->d;
     const size_t B = (size_t)h->B;
     const size_t lds = vf_lds_bytes(h);
-    if (lds > 160 * 1024) return fail("upr_batch_value_function_update: working set exceeds 160 KiB of LDS");
+    if (lds > 160 * 1024) return upr_fail("upr_batch_value_function_update: working set exceeds 160 KiB of LDS");
     if (vf_alloc(h)) return 1;
     h->vf_state = 0; h->vf_tracked = false; h->vf_ms_pending = false;
     // statistics and dispatch keys of the solve are put back behind the query's QP (what upr_batch_hold_stats does, on a snapshot
@@ -1745,13 +1222,13 @@ int upr_batch_value_function_update_interface(upr_batch* h) {
  * refused here -- upr_batch_value_function_update_interface is the same update for such a handle. */
 int upr_batch_value_function_update(upr_batch* h) {
     UPR_ENTER(h);
-    if (h->P.n_dyn) return fail("upr_batch_value_function_update: not available with a dynamic obstacle (interface states): upr_batch_value_function_update_interface takes such a handle");
+    if (h->P.n_dyn) return upr_fail("upr_batch_value_function_update: not available with a dynamic obstacle (interface states): upr_batch_value_function_update_interface takes such a handle");
     return upr_batch_value_function_update_interface(h);
 }
 
 static int vf_ready(const upr_batch* h, const char* who) {
-    if (h->vf_state == 0) return fail(std::string(who) + ": no upr_batch_value_function_update on this handle yet");
-    if (h->vf_state == 2) return fail(std::string(who) + ": the cost-to-go is stale (the plan or the observation changed since upr_batch_value_function_update)");
+    if (h->vf_state == 0) return upr_fail(std::string(who) + ": no upr_batch_value_function_update on this handle yet");
+    if (h->vf_state == 2) return upr_fail(std::string(who) + ": the cost-to-go is stale (the plan or the observation changed since upr_batch_value_function_update)");
     return 0;
 }
 
@@ -1766,7 +1243,7 @@ int upr_batch_track_value_function(upr_batch* h, int on) {
     }
     if (h->vf_track) return 0;
     const size_t lds = vf_lds_bytes(h);
-    if (lds > 160 * 1024) return fail("upr_batch_track_value_function: working set exceeds 160 KiB of LDS");
+    if (lds > 160 * 1024) return upr_fail("upr_batch_track_value_function: working set exceeds 160 KiB of LDS");
     if (vf_alloc(h)) return 1;
     if (h->qp.exported && !h->kkt && dev_alloc(&h->kkt, (size_t)h->B * h->qp.stride)) return 1;
     if (lds > 64 * 1024) UPR_HIP(vf_raise_lds_limit());
@@ -1778,7 +1255,7 @@ int upr_batch_value_function(upr_batch* h, int n, const int* inst, const double*
     UPR_ENTER(h);
     if (vf_ready(h, "upr_batch_value_function")) return 1;
     if (n <= 0) return 0;
-    if (!inst || !t || !x) return fail("upr_batch_value_function: null argument");
+    if (!inst || !t || !x) return upr_fail("upr_batch_value_function: null argument");
     const upr_dims& d = h->d;
     point_upload pts;
     if (pts.up(h, n, inst, t)) return 1;
@@ -1811,7 +1288,7 @@ int upr_batch_equality_lagrangian(upr_batch* h, int n, const int* inst, const do
     UPR_ENTER(h);
     if (vf_ready(h, "upr_batch_equality_lagrangian")) return 1;
     if (n <= 0) return 0;
-    if (!inst || !t || !nu_out) return fail("upr_batch_equality_lagrangian: null argument");
+    if (!inst || !t || !nu_out) return upr_fail("upr_batch_equality_lagrangian: null argument");
     const upr_dims& d = h->d;
     point_upload pts;
     if (pts.up(h, n, inst, t)) return 1;
@@ -1850,116 +1327,6 @@ double upr_batch_value_function_ms(upr_batch* h) {
     return h->vf_ms;
 }
 
-// the balance family: every entry names its request ("balance family" above)
-int upr_batch_balance_points_mu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, const double* mu_scale,
-                                double* rho, double* z, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_balance_points", .needs = "x, params and rho must not be NULL", .n = n, .x = x, .n_scen = n_scen,
-                            .params = params, .per = per_point != 0, .scale = mu_scale ? BAL_MU_SCENARIO : BAL_MU_NONE, .mu_scale = mu_scale,
-                            .out = rho, .z = z, .iters = iters});
-}
-int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double* rho, double* z, int* iters) {
-    return upr_batch_balance_points_mu(h, n, x, n_scen, params, per_point, nullptr, rho, z, iters);
-}
-
-int upr_batch_balance_plan_mu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_balance_plan", .needs = "rho must not be NULL", .plan = true, .n_scen = n_scen, .params = params,
-                            .per = per_instance != 0, .scale = mu_scale ? BAL_MU_SCENARIO : BAL_MU_NONE, .mu_scale = mu_scale, .out = rho, .iters = iters});
-}
-int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double* rho, int* iters) {
-    return upr_batch_balance_plan_mu(h, n_scen, params, per_instance, nullptr, rho, iters);
-}
-
-int upr_batch_friction_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double kappa_max,
-                                     double* kappa_hi, double* kappa_lo, double* z, double* y, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_friction_margin_points", .needs = "x, params and kappa_hi must not be NULL", .n = n, .x = x, .n_scen = n_scen,
-                            .params = params, .per = per_point != 0, .quantity = BAL_MARGIN, .kappa_max = kappa_max, .out = kappa_hi, .kappa_lo = kappa_lo,
-                            .z = z, .y = y, .iters = iters});
-}
-
-int upr_batch_friction_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double kappa_max, double* kappa_hi,
-                                   double* kappa_lo, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_friction_margin_plan", .needs = "kappa_hi must not be NULL", .plan = true, .n_scen = n_scen, .params = params,
-                            .per = per_instance != 0, .quantity = BAL_MARGIN, .kappa_max = kappa_max, .out = kappa_hi, .kappa_lo = kappa_lo, .iters = iters});
-}
-
-int upr_batch_balance_points_cmu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, const double* mu_scale_c,
-                                 double* rho, double* z, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_balance_points_cmu", .needs = "x, params, mu_scale_c and rho must not be NULL", .n = n, .x = x,
-                            .n_scen = n_scen, .params = params, .per = per_point != 0, .scale = BAL_MU_CONTACT, .mu_scale = mu_scale_c, .out = rho, .z = z,
-                            .iters = iters});
-}
-
-int upr_batch_balance_plan_cmu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale_c, double* rho, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_balance_plan_cmu", .needs = "mu_scale_c and rho must not be NULL", .plan = true, .n_scen = n_scen,
-                            .params = params, .per = per_instance != 0, .scale = BAL_MU_CONTACT, .mu_scale = mu_scale_c, .out = rho, .iters = iters});
-}
-
-int upr_batch_friction_margin_groups_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, int n_grp,
-                                            const unsigned* group_mask, const double* mu_base, double kappa_max, double* kappa_hi, double* kappa_lo,
-                                            double* z, double* y, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_friction_margin_groups_points", .needs = "x, params and kappa_hi must not be NULL", .n = n, .x = x,
-                            .n_scen = n_scen, .params = params, .per = per_point != 0, .quantity = BAL_MARGIN_GROUPS, .kappa_max = kappa_max, .n_grp = n_grp,
-                            .group_mask = group_mask, .mu_base = mu_base, .out = kappa_hi, .kappa_lo = kappa_lo, .z = z, .y = y, .iters = iters});
-}
-
-int upr_batch_friction_margin_groups_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_grp, const unsigned* group_mask,
-                                          const double* mu_base, double kappa_max, double* kappa_hi, double* kappa_lo, int* iters, double* worst,
-                                          int* worst_knot) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_friction_margin_groups_plan", .needs = "kappa_hi and worst must not both be NULL", .plan = true,
-                            .n_scen = n_scen, .params = params, .per = per_instance != 0, .quantity = BAL_MARGIN_GROUPS, .kappa_max = kappa_max,
-                            .n_grp = n_grp, .group_mask = group_mask, .mu_base = mu_base, .out = kappa_hi, .kappa_lo = kappa_lo, .iters = iters,
-                            .worst = worst, .worst_knot = worst_knot});
-}
-
-int upr_batch_speed_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double s_max, double* speed,
-                                  double* z, double* y, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_speed_margin_points", .needs = "x, params and speed must not be NULL", .n = n, .x = x, .n_scen = n_scen,
-                            .params = params, .per = per_point != 0, .quantity = BAL_SPEED, .s_max = s_max, .out = speed, .z = z, .y = y, .iters = iters});
-}
-
-int upr_batch_speed_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double s_max, double* speed, int* iters,
-                                double* window, int* knot, double* limit) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_speed_margin_plan", .needs = "speed and window must not both be NULL", .plan = true, .n_scen = n_scen,
-                            .params = params, .per = per_instance != 0, .quantity = BAL_SPEED, .s_max = s_max, .limit = limit, .out = speed, .iters = iters,
-                            .worst = window, .worst_knot = knot});
-}
-
-int upr_batch_path_accel_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double d_max, double speed,
-                                       double* accel, double* z, double* y, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_path_accel_margin_points", .needs = "x, params and accel must not be NULL", .n = n, .x = x, .n_scen = n_scen,
-                            .params = params, .per = per_point != 0, .quantity = BAL_PATHACC, .d_max = d_max, .speed = speed, .out = accel, .z = z, .y = y,
-                            .iters = iters});
-}
-
-int upr_batch_path_accel_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double d_max, double speed, double* accel, int* iters,
-                                     double* window, int* knot, double* limit) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_path_accel_margin_plan", .needs = "accel and window must not both be NULL", .plan = true, .n_scen = n_scen,
-                            .params = params, .per = per_instance != 0, .quantity = BAL_PATHACC, .limit = limit, .d_max = d_max, .speed = speed, .out = accel,
-                            .iters = iters, .worst = window, .worst_knot = knot});
-}
-
-int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, int start_level, int end_level,
-                          int common, int boxes, double* duration, int* level, int* reach, unsigned* edges, int* iters) {
-    UPR_ENTER(h);
-    return balance_call(h, {.who = "upr_batch_retime_plan", .needs = "duration and level must not both be NULL", .plan = true, .n_scen = n_scen, .params = params,
-                            .per = per_instance != 0, .quantity = BAL_RETIME, .speeds = speeds, .n_lvl = n_lvl, .start = start_level, .end = end_level,
-                            .common = common != 0, .boxes = boxes != 0, .level = level, .reach = reach, .edges = edges, .out = duration, .iters = iters});
-}
-
-double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }
-
 int upr_batch_device_ptrs(upr_batch* h, void** xs, void** us) {
     UPR_ENTER(h);
     if (xs) *xs = h->xs;
@@ -1974,7 +1341,7 @@ int upr_batch_qp_profile(upr_batch* h, double* out) {
     {
         const char* f = getenv("UPR_JIT_FLAGS");
         if (!h->qp.jit || !f || !strstr(f, "-DUPR_QP3_PROF"))
-            return fail("upr_batch_qp_profile: the phase stamps exist in run-time instantiations only: create the handle with UPR_QP3_JIT=2 UPR_JIT_FLAGS=-DUPR_QP3_PROF");
+            return upr_fail("upr_batch_qp_profile: the phase stamps exist in run-time instantiations only: create the handle with UPR_QP3_JIT=2 UPR_JIT_FLAGS=-DUPR_QP3_PROF");
     }
     if (!h->prof) { if (dev_alloc(&h->prof, (size_t)h->B * 64)) return 1; return 0; }
     UPR_HIP(hipStreamSynchronize(h->stream));
@@ -2029,8 +1396,8 @@ int upr_batch_copy_solution_device(upr_batch* h, void* xs_dst, void* us_dst) {
 
 int upr_batch_copy_policy_device(upr_batch* h, void* u_dst) {
     UPR_ENTER(h);
-    if (!h->ev_u) return fail("upr_batch_copy_policy_device: no tick has run on this handle");
-    if (!u_dst) return fail("upr_batch_copy_policy_device: null destination");
+    if (!h->ev_u) return upr_fail("upr_batch_copy_policy_device: no tick has run on this handle");
+    if (!u_dst) return upr_fail("upr_batch_copy_policy_device: null destination");
     UPR_HIP(hipMemcpyAsync(u_dst, h->ev_u, sizeof(double) * h->B * h->d.nu, hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
@@ -2041,7 +1408,7 @@ int upr_set_device(int device) {
     if (need_device()) return 1;
     int n = 0;
     UPR_HIP(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) return fail("upr_set_device: no such device");
+    if (device < 0 || device >= n) return upr_fail("upr_set_device: no such device");
     UPR_HIP(hipSetDevice(device));
     return 0;
 }
@@ -2125,7 +1492,7 @@ int upr_batch_evaluate_policy(upr_batch* h, const double* t, int t_stride, const
 
 int upr_batch_tick(upr_batch* h, const double* t, int t_stride, const double* x, double* x_out, double* u_out, double* stats_out) {
     UPR_ENTER(h);
-    if (!t || !x || !x_out || !u_out) return fail("upr_batch_tick: null argument");
+    if (!t || !x || !x_out || !u_out) return upr_fail("upr_batch_tick: null argument");
     if (h->vf_state) h->vf_state = 2;
     const upr_dims& d = h->d;
     const size_t B = (size_t)h->B, nx = (size_t)d.nx, nu = (size_t)d.nu, ndyn = upr_iface_dyn_width(h->P.n_dyn);
@@ -2238,29 +1605,8 @@ int upr_batch_qp_kkt(upr_batch* h, double* dxs, double* dus, double* pi, double*
 
 int upr_batch_set_projectile_flag(upr_batch* h, const double* sflag) {
     UPR_ENTER(h);
-    if (!h->pflag) return fail("upr_batch_set_projectile_flag: the problem has no dynamic obstacle");
+    if (!h->pflag) return upr_fail("upr_batch_set_projectile_flag: the problem has no dynamic obstacle");
     UPR_HIP(hipMemcpy(h->pflag, sflag, sizeof(double) * h->B, hipMemcpyHostToDevice));
     return 0;
 }
 }  // extern "C"
-
-#ifdef UPR_LS_PROF
-// instrumented build only: cycles from the start of the line-search kernel to each of its stamps, summed over workgroups, [15] = workgroups
-extern "C" int upr_debug_ls_prof(double* out, int reset) {
-    unsigned long long h[16];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(upr_ls_prof), sizeof(h)) != hipSuccess) return 1;
-    for (int i = 0; i < 16; ++i) out[i] = (double)h[i];
-    if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(upr_ls_prof), z, sizeof(z)) != hipSuccess) return 1; }
-    return 0;
-}
-#endif
-#ifdef UPR_LIN_PROF
-// instrumented build only: cycles per phase of the linearisation kernel summed over workgroups, [7] = workgroups counted
-extern "C" int upr_debug_lin_prof(double* out, int reset) {
-    unsigned long long h[8];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(upr_lin_prof), sizeof(h)) != hipSuccess) return 1;
-    for (int i = 0; i < 8; ++i) out[i] = (double)h[i];
-    if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(upr_lin_prof), z, sizeof(z)) != hipSuccess) return 1; }
-    return 0;
-}
-#endif

@@ -1,0 +1,379 @@
+// upr_api_balance.hip -- the balance family of libupright_mi.so (include/upright_mi.h): request, validation, launcher and the
+// fifteen entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan with upr_batch_balance_ms.  The one unit that includes
+// upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h and upr_retime.h: their kernels are defined here and nowhere else.
+// What crosses to upr_api.hip (upr_handle.h): upr_bal_resolve, the part of upr_batch_create that fills the handle's choice of form;
+// from there it takes upr_fail.  The family reads and writes the handle's bal, bal_buf / bal_cap, bal_ev and bal_ms, nothing else.
+#include "upr_handle.h"
+
+#include <cmath>
+
+#include "upr_balance.h"
+#include "upr_margin.h"
+#include "upr_speed.h"
+#include "upr_pathacc.h"
+#include "upr_retime.h"
+
+// the form of a handle's balance family (UPR_BAL_FORM=0: the wave form for the one-body shapes too; tests)
+void upr_bal_resolve(upr_batch* h) {
+    const upr_dims& d = h->d;
+    const char* e = getenv("UPR_BAL_FORM");
+    h->bal.L = upr_bal_layout(d.nb, d.nc, d.nf);
+    h->bal.lds = (size_t)h->bal.L.total * sizeof(double);
+    h->bal.form = (upr_bal_lane_form(d.nb) && !(e && atoi(e) == 0)) ? BAL_LANE : BAL_WAVE;
+}
+
+namespace {
+
+// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h): the fifteen entry points end here, in balance_call.  An entry fills a REQUEST, which
+// names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
+// go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
+// the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
+// it carves the scratch block region by region, noting with every region what is copied into it before the kernels and out of it
+// after them, and takes the kernel from a table by form and quantity.  Everything is enqueued on the handle's stream behind
+// whatever is in flight and the one synchronisation is the last statement.  The scratch of the calls is one block on the handle
+// that serves nothing else and only grows (bal_buf): a call in the steady state allocates and frees nothing.
+enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
+// the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h) | the
+// path-acceleration margin (upr_pathacc.h) | the retiming of a plan on a speed lattice (upr_retime.h)
+enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5 };
+struct bal_request {
+    const char* who = "";     // the entry, as its messages name it
+    const char* needs = "";   // ... and what they say about its required pointers
+    // the points: the knots of the handle's plan where they lie on the device, or n states x [n][3 nq] on the host
+    bool plan = false; int n = 0; const double* x = nullptr;
+    // the scenarios: parameter blocks on the host, [n_scen][nb][10] for all points or (per) a set of their own for every point /
+    // every instance of the plan.  NULL (plan, n_scen == 1): every instance against its own body parameters
+    int n_scen = 0; const double* params = nullptr; bool per = false;
+    // the friction scale of every scenario (BAL_RHO)
+    int scale = BAL_MU_NONE; const double* mu_scale = nullptr;
+    // the quantity.  The margins (upr_margin.h) run on the same jobs: out is kappa_hi, z the multipliers there, iters the solves
+    // over all evaluations.  Per group every output gains a trailing [n_grp]; mu_base: the scales of the contacts outside the group
+    // ([n_scen][nc]; NULL: ones)
+    int quantity = BAL_RHO; double kappa_max = 0.0; int n_grp = 1; const unsigned* group_mask = nullptr; const double* mu_base = nullptr;
+    // the speed margin: out is speed, four doubles per job; z and y hold two certificates per job, the lower end first; worst /
+    // worst_knot ([B][n_scen][2]; plan) are the window over the knots and the knots that attain it, limit [B] the limit speed
+    double s_max = 0.0; double* limit = nullptr;
+    // the path-acceleration margin: out is accel, four doubles per job, certificates and reductions as the speed margin's; the range
+    // [-d_max, d_max] of sddot at sdot = speed; limit [B][2] the interval of sddot the acceleration boxes allow
+    double d_max = 0.0, speed = 1.0;
+    // the retiming (plan only): the lattice speeds [n_lvl]; start / end a level or -1; common: one time law under all scenarios;
+    // boxes: the velocity and acceleration boxes cut edges.  out is duration, one double per (instance, scenario) or per instance
+    // with common; level [..][N + 1], reach [..][2]; edges [B][n_scen][N][n_lvl] and iters, one per mask row, stay per scenario
+    const double* speeds = nullptr; int n_lvl = 0, start = -1, end = -1; bool common = false, boxes = true;
+    int *level = nullptr, *reach = nullptr; unsigned* edges = nullptr;
+    // the answers on the host; all but the required ones may be NULL.  worst / worst_knot ([B][n_scen][n_grp]; plan, per group): the
+    // largest kappa_hi over the knots of an instance, reduced on the device; out may then be NULL and kappa_hi stays on the device
+    double* out = nullptr;   // rho | kappa_hi
+    double *kappa_lo = nullptr, *z = nullptr, *y = nullptr; int* iters = nullptr; double* worst = nullptr; int* worst_knot = nullptr;
+};
+long long bal_points(const upr_batch* h, const bal_request& r) { return r.plan ? (long long)h->B * (h->d.N + 1) : r.n; }
+size_t bal_param_sets(const upr_batch* h, const bal_request& r) { return (size_t)(r.per ? (r.plan ? h->B : r.n) : 1) * r.n_scen; }
+
+size_t bal_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// the next region of a scratch block of `total` bytes so far: its offset (a region that is not wanted takes no room)
+size_t bal_take(size_t& total, size_t bytes, bool wanted) { const size_t o = total; total += wanted ? bal_up(bytes) : 0; return o; }
+int balance_scratch(upr_batch* h, size_t bytes) {
+    if (bytes <= h->bal_cap) return 0;
+    if (h->bal_buf) { UPR_HIP(hipFree(h->bal_buf)); h->bal_buf = nullptr; h->bal_cap = 0; }
+    UPR_HIP(hipMalloc(&h->bal_buf, bytes));
+    h->bal_cap = bytes;
+    return 0;
+}
+int balance_check_groups(const upr_batch* h, int n_grp, const unsigned* group_mask) {
+    if (n_grp < 1 || n_grp > 65535) return upr_fail("friction margin of contact groups: n_grp must be in 1 .. 65535");
+    if (!group_mask) return upr_fail("friction margin of contact groups: group_mask must not be NULL");
+    const int nc = h->d.nc;
+    for (int g = 0; g < n_grp; ++g) {
+        if (group_mask[g] == 0u) return upr_fail("friction margin of contact groups: group " + std::to_string(g) + " has an empty mask");
+        if (nc < 32 && (group_mask[g] >> nc) != 0u)
+            return upr_fail("friction margin of contact groups: group " + std::to_string(g) + " has a mask bit >= nc = " + std::to_string(nc));
+    }
+    return 0;
+}
+int balance_check_scales(const double* v, size_t count, const char* what) {
+    if (v) for (size_t i = 0; i < count; ++i)
+        if (!(v[i] >= 0) || !std::isfinite(v[i])) return upr_fail(std::string("balance check: every ") + what + " must be finite and >= 0");
+    return 0;
+}
+// 0: a request to launch; 1: refused (upr_last_error says why); 2: no points, nothing to do
+int balance_validate(const upr_batch* h, const bal_request& r) {
+    const upr_dims& d = h->d;
+    auto refuse = [&](const char* why) { return upr_fail(std::string(r.who) + ": " + why); };
+    const bool margin = r.quantity == BAL_MARGIN || r.quantity == BAL_MARGIN_GROUPS;
+    if (margin && (!(r.kappa_max > 0) || !std::isfinite(r.kappa_max))) return upr_fail("friction margin: kappa_max must be finite and > 0");
+    if (r.quantity == BAL_SPEED && (!(r.s_max > 1) || !std::isfinite(r.s_max))) return upr_fail("speed margin: s_max must be finite and > 1");
+    if (r.quantity == BAL_PATHACC && (!(r.d_max > 0) || !std::isfinite(r.d_max) || !(r.speed >= 0) || !std::isfinite(r.speed)))
+        return upr_fail("path-acceleration margin: d_max must be finite and > 0, speed finite and >= 0");
+    if (r.quantity == BAL_MARGIN_GROUPS && balance_check_groups(h, r.n_grp, r.group_mask)) return 1;
+    if (!r.plan && r.n <= 0) return 2;
+    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst && !r.level)) return refuse(r.needs);
+    if (r.plan && !r.params) {
+        if (r.n_scen != 1) return refuse("params == NULL needs n_scen == 1 (every instance's own body parameters)");
+    } else if (r.n_scen < 1) return refuse("n_scen must be >= 1");
+    if (r.params) for (size_t i = 0, e = bal_param_sets(h, r) * d.nb; i < e; ++i)
+        if (!(r.params[10 * i] > 0) || !std::isfinite(r.params[10 * i])) return upr_fail("balance check: every body of every scenario needs a positive finite mass");
+    if (balance_check_scales(r.mu_scale, (size_t)r.n_scen * (r.scale == BAL_MU_CONTACT ? d.nc : 1), "mu_scale")) return 1;
+    if (balance_check_scales(r.mu_base, (size_t)r.n_scen * d.nc, "mu_base")) return 1;
+    const long long n = bal_points(h, r);
+    if (n > (1ll << 31) - 64 || n * r.n_scen * r.n_grp > (1ll << 36)) return upr_fail("balance check: too many points");
+    if (r.quantity == BAL_RETIME) {
+        bool ok = r.speeds && r.n_lvl >= 1 && r.n_lvl <= UPR_RET_MAX_LEVELS;
+        for (int m = 0; ok && m < r.n_lvl; ++m) ok = std::isfinite(r.speeds[m]) && r.speeds[m] >= 0 && (m == 0 || r.speeds[m] > r.speeds[m - 1]);
+        if (!ok) return upr_fail("retime: speeds must be 1 .. 32 finite values >= 0 in strictly increasing order");
+        if (r.start < -1 || r.start >= r.n_lvl || r.end < -1 || r.end >= r.n_lvl) return upr_fail("retime: start and end must be -1 or a level index");
+        if (n * r.n_scen * r.n_lvl > (1ll << 36)) return upr_fail("balance check: too many points");   // (the jobs: a mask row each)
+    }
+    return 0;
+}
+
+// form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
+// group, the speed margin, the path-acceleration margin, the edge masks of the retiming.  Every kernel takes (its record, upr_bal_dims,
+// long long jobs); the record is upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the groups, upr_spd_args for the
+// speed margin, upr_pac_args for the path-acceleration margin and upr_ret_args for the retiming.
+const void* const bal_kernels[2][8] = {
+    /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
+                    (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel,
+                    (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel},
+    /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
+                    (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel,
+                    (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel}};
+struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
+
+int balance_launch(upr_batch* h, const bal_request& r) {
+    const upr_dims& d = h->d;
+    upr_bal_dims L = h->bal.L;
+    const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, speed = r.quantity == BAL_SPEED || pathacc;   // (speed: the four-double layout)
+    const bool retime = r.quantity == BAL_RETIME;
+    const bool margin = r.quantity != BAL_RHO && !speed && !retime, groups = r.quantity == BAL_MARGIN_GROUPS;
+    // (the retiming: a job is a mask row, (instance, scenario, segment, level); nplans outputs of the path kernel)
+    const long long n = bal_points(h, r), njobs = retime ? (long long)h->B * r.n_scen * d.N * r.n_lvl : n * r.n_scen, ng = r.n_grp, nout = njobs * ng;
+    const long long nplans = retime ? (long long)h->B * (r.common ? 1 : r.n_scen) : 0;
+    const bool want_worst = r.worst || r.worst_knot;
+    const long long nworst = want_worst ? (long long)h->B * r.n_scen * (speed ? 2 : ng) : 0;
+    const size_t per_out = speed ? 4 : 1, ends = speed ? 2 : 1;   // doubles of `out` and certificates per job
+    const double* scale_host = groups ? r.mu_base : r.mu_scale;
+    const size_t scale_count = (size_t)r.n_scen * ((groups || r.scale == BAL_MU_CONTACT) ? d.nc : 1);
+    // the scratch block, region by region, with what goes into a region before the kernels (from) and out of it after them (to)
+    bal_copy up[4], down[8];
+    int nup = 0, ndown = 0; size_t total = 0;
+    auto region = [&](size_t bytes, bool wanted, const void* from, void* to) {
+        const size_t o = bal_take(total, bytes, wanted);
+        if (wanted && from) up[nup++] = {o, const_cast<void*>(from), bytes};
+        if (wanted && to) down[ndown++] = {o, to, bytes};
+        return o;
+    };
+    const size_t o_st = region(sizeof(double) * n * UPR_BAL_ST, true, nullptr, nullptr);
+    const size_t o_rho = region(sizeof(double) * (retime ? nplans : nout * per_out), true, nullptr, r.out);
+    const size_t o_z = region(sizeof(double) * nout * ends * L.ncol, r.z != nullptr, nullptr, r.z);
+    const size_t o_it = region(sizeof(int) * nout, r.iters != nullptr, nullptr, r.iters);
+    const size_t o_par = region(sizeof(double) * bal_param_sets(h, r) * d.nb * 10, r.params != nullptr, r.params, nullptr);
+    const size_t o_x = region(sizeof(double) * n * d.nx, !r.plan, r.x, nullptr);
+    const size_t o_mu = region(sizeof(double) * scale_count, scale_host != nullptr, scale_host, nullptr);
+    const size_t o_lo = region(sizeof(double) * nout, r.kappa_lo != nullptr, nullptr, r.kappa_lo);
+    const size_t o_y = region(sizeof(double) * nout * ends * L.m, r.y != nullptr, nullptr, r.y);
+    const size_t o_gm = region(sizeof(unsigned) * ng, groups, r.group_mask, nullptr);
+    const size_t o_w = region(sizeof(double) * nworst, want_worst, nullptr, r.worst);
+    const size_t o_wk = region(sizeof(int) * nworst, want_worst, nullptr, r.worst_knot);
+    const size_t o_lim = region(sizeof(double) * h->B * (pathacc ? 2 : 1), r.limit != nullptr, nullptr, r.limit);
+    const size_t o_vee = region(sizeof(double) * n * 3, pathacc || retime, nullptr, nullptr);
+    const size_t o_spd = region(sizeof(double) * r.n_lvl, retime, r.speeds, nullptr);
+    const size_t o_edg = region(sizeof(unsigned) * nout, retime, nullptr, r.edges);
+    const size_t o_arg = region((size_t)nplans * d.N * r.n_lvl, retime, nullptr, nullptr);
+    const size_t o_lvl = region(sizeof(int) * nplans * (d.N + 1), retime, nullptr, r.level);
+    const size_t o_rch = region(sizeof(int) * nplans * 2, retime && r.reach, nullptr, r.reach);
+    if (balance_scratch(h, total)) return 1;
+    char* base = (char*)h->bal_buf;
+    for (int i = 0; i < nup; ++i) UPR_HIP(hipMemcpyAsync(base + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, h->stream));
+    if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
+    UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
+    const double* dx = r.plan ? h->xs : (const double*)(base + o_x);
+    double *dst = (double*)(base + o_st), *drho = (double*)(base + o_rho);
+    const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
+    if ((pathacc || retime) && h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_vee_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
+    else if (pathacc || retime) hipLaunchKernelGGL(upr_bal_state_vee_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
+    else if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
+    else hipLaunchKernelGGL(upr_bal_state_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
+    UPR_HIP(hipGetLastError());
+    upr_bal_args A;
+    A.P = h->dP; A.n = (int)n; A.n_scen = r.n_scen; A.st = dst; A.eq_scale = d.eq_scale;
+    A.params = r.params ? (const double*)(base + o_par) : h->body_params;
+    A.pdiv = r.plan ? ((r.per || !r.params) ? d.N + 1 : 0) : (r.per ? 1 : 0);   // points that share a parameter set
+    A.rho = drho; A.z = r.z ? (double*)(base + o_z) : nullptr; A.iters = r.iters ? (int*)(base + o_it) : nullptr;
+    A.mu_scale = r.mu_scale ? (const double*)(base + o_mu) : nullptr;
+    upr_mar_args M;
+    if (margin) {
+        M.J = A; M.J.rho = nullptr; M.kappa_max = r.kappa_max; M.kappa_hi = drho;
+        M.kappa_lo = r.kappa_lo ? (double*)(base + o_lo) : nullptr; M.y = r.y ? (double*)(base + o_y) : nullptr;
+    }
+    upr_spd_args S;
+    if (speed && !pathacc) { S.J = A; S.J.rho = nullptr; S.s_max = r.s_max; S.speed = drho; S.y = r.y ? (double*)(base + o_y) : nullptr; }
+    upr_pac_args C;
+    if (pathacc) {
+        C.J = A; C.J.rho = nullptr; C.d_max = r.d_max; C.speed = r.speed; C.vee = (const double*)(base + o_vee); C.accel = drho;
+        C.y = r.y ? (double*)(base + o_y) : nullptr;
+    }
+    upr_ret_args T;
+    if (retime) {
+        T.J = A; T.J.rho = nullptr; T.vee = (const double*)(base + o_vee); T.xs = dx; T.speeds = (const double*)(base + o_spd); T.M = r.n_lvl;
+        T.nk = d.N + 1; T.nx = d.nx; T.boxes = r.boxes ? 1 : 0; T.h = h->P.dt; T.edges = (unsigned*)(base + o_edg);
+    }
+    upr_grp_args X;
+    if (groups) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = r.mu_base ? (const double*)(base + o_mu) : nullptr; }
+    // lane form: 64 jobs per workgroup, the groups on the y axis.  Wave form: a workgroup is one wave and the jobs (for the groups:
+    // job x group) are dealt round robin to a grid that fills the device a few times over (its LDS, at most 26.4 KB, lets six of
+    // the largest shape share a CU inside the 160 KiB)
+    long long count = (wave && groups) ? nout : njobs;
+    const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
+    void* args[] = {retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
+    UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
+    if (retime) {
+        upr_ret_path_args Q;
+        Q.edges = T.edges; Q.speeds = T.speeds; Q.M = r.n_lvl; Q.nk = d.N + 1; Q.n_scen = r.n_scen; Q.common = r.common ? 1 : 0; Q.start = r.start; Q.end = r.end;
+        Q.h = h->P.dt; Q.arg = (unsigned char*)(base + o_arg); Q.duration = drho; Q.level = (int*)(base + o_lvl); Q.reach = r.reach ? (int*)(base + o_rch) : nullptr;
+        hipLaunchKernelGGL(upr_bal_retime_path_kernel, dim3((unsigned)(nplans < 16384 ? nplans : 16384)), dim3(64), 0, h->stream, Q, nplans);
+        UPR_HIP(hipGetLastError());
+    } else if (pathacc && (want_worst || r.limit)) {
+        const long long lanes = nworst + (r.limit ? h->B : 0);
+        hipLaunchKernelGGL(upr_bal_pathacc_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
+                           d.N + 1, r.n_scen, nworst, h->B, d.nx, r.speed, (const double*)h->xs, (double*)(base + o_w),
+                           r.worst_knot ? (int*)(base + o_wk) : nullptr, r.limit ? (double*)(base + o_lim) : nullptr);
+        UPR_HIP(hipGetLastError());
+    } else if (speed && (want_worst || r.limit)) {
+        const long long lanes = nworst + (r.limit ? h->B : 0);
+        hipLaunchKernelGGL(upr_bal_speed_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
+                           d.N + 1, r.n_scen, nworst, h->B, d.nx, d.nu, (const double*)h->xs, (const double*)h->us, (double*)(base + o_w),
+                           r.worst_knot ? (int*)(base + o_wk) : nullptr, r.limit ? (double*)(base + o_lim) : nullptr);
+        UPR_HIP(hipGetLastError());
+    } else if (want_worst) {
+        hipLaunchKernelGGL(upr_bal_margin_worst_kernel, dim3((unsigned)((nworst + 63) / 64)), dim3(64), 0, h->stream, (const double*)drho, d.N + 1,
+                           (long long)r.n_scen * ng, nworst, (double*)(base + o_w), r.worst_knot ? (int*)(base + o_wk) : nullptr);
+        UPR_HIP(hipGetLastError());
+    }
+    UPR_HIP(hipEventRecord(h->bal_ev[1], h->stream));
+    for (int i = 0; i < ndown; ++i) UPR_HIP(hipMemcpyAsync(down[i].host, base + down[i].off, down[i].bytes, hipMemcpyDeviceToHost, h->stream));
+    UPR_HIP(hipStreamSynchronize(h->stream));
+    float ms = 0.0f;
+    UPR_HIP(hipEventElapsedTime(&ms, h->bal_ev[0], h->bal_ev[1]));
+    h->bal_ms = ms;
+    return 0;
+}
+int balance_call(upr_batch* h, const bal_request& r) {
+    if (const int v = balance_validate(h, r)) return v == 1;
+    return balance_launch(h, r);
+}
+
+}  // namespace
+
+extern "C" {
+
+// the balance family: every entry names its request ("balance family" above)
+int upr_batch_balance_points_mu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, const double* mu_scale,
+                                double* rho, double* z, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_balance_points", .needs = "x, params and rho must not be NULL", .n = n, .x = x, .n_scen = n_scen,
+                            .params = params, .per = per_point != 0, .scale = mu_scale ? BAL_MU_SCENARIO : BAL_MU_NONE, .mu_scale = mu_scale,
+                            .out = rho, .z = z, .iters = iters});
+}
+int upr_batch_balance_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double* rho, double* z, int* iters) {
+    return upr_batch_balance_points_mu(h, n, x, n_scen, params, per_point, nullptr, rho, z, iters);
+}
+
+int upr_batch_balance_plan_mu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale, double* rho, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_balance_plan", .needs = "rho must not be NULL", .plan = true, .n_scen = n_scen, .params = params,
+                            .per = per_instance != 0, .scale = mu_scale ? BAL_MU_SCENARIO : BAL_MU_NONE, .mu_scale = mu_scale, .out = rho, .iters = iters});
+}
+int upr_batch_balance_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double* rho, int* iters) {
+    return upr_batch_balance_plan_mu(h, n_scen, params, per_instance, nullptr, rho, iters);
+}
+
+int upr_batch_friction_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double kappa_max,
+                                     double* kappa_hi, double* kappa_lo, double* z, double* y, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_friction_margin_points", .needs = "x, params and kappa_hi must not be NULL", .n = n, .x = x, .n_scen = n_scen,
+                            .params = params, .per = per_point != 0, .quantity = BAL_MARGIN, .kappa_max = kappa_max, .out = kappa_hi, .kappa_lo = kappa_lo,
+                            .z = z, .y = y, .iters = iters});
+}
+
+int upr_batch_friction_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double kappa_max, double* kappa_hi,
+                                   double* kappa_lo, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_friction_margin_plan", .needs = "kappa_hi must not be NULL", .plan = true, .n_scen = n_scen, .params = params,
+                            .per = per_instance != 0, .quantity = BAL_MARGIN, .kappa_max = kappa_max, .out = kappa_hi, .kappa_lo = kappa_lo, .iters = iters});
+}
+
+int upr_batch_balance_points_cmu(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, const double* mu_scale_c,
+                                 double* rho, double* z, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_balance_points_cmu", .needs = "x, params, mu_scale_c and rho must not be NULL", .n = n, .x = x,
+                            .n_scen = n_scen, .params = params, .per = per_point != 0, .scale = BAL_MU_CONTACT, .mu_scale = mu_scale_c, .out = rho, .z = z,
+                            .iters = iters});
+}
+
+int upr_batch_balance_plan_cmu(upr_batch* h, int n_scen, const double* params, int per_instance, const double* mu_scale_c, double* rho, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_balance_plan_cmu", .needs = "mu_scale_c and rho must not be NULL", .plan = true, .n_scen = n_scen,
+                            .params = params, .per = per_instance != 0, .scale = BAL_MU_CONTACT, .mu_scale = mu_scale_c, .out = rho, .iters = iters});
+}
+
+int upr_batch_friction_margin_groups_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, int n_grp,
+                                            const unsigned* group_mask, const double* mu_base, double kappa_max, double* kappa_hi, double* kappa_lo,
+                                            double* z, double* y, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_friction_margin_groups_points", .needs = "x, params and kappa_hi must not be NULL", .n = n, .x = x,
+                            .n_scen = n_scen, .params = params, .per = per_point != 0, .quantity = BAL_MARGIN_GROUPS, .kappa_max = kappa_max, .n_grp = n_grp,
+                            .group_mask = group_mask, .mu_base = mu_base, .out = kappa_hi, .kappa_lo = kappa_lo, .z = z, .y = y, .iters = iters});
+}
+
+int upr_batch_friction_margin_groups_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_grp, const unsigned* group_mask,
+                                          const double* mu_base, double kappa_max, double* kappa_hi, double* kappa_lo, int* iters, double* worst,
+                                          int* worst_knot) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_friction_margin_groups_plan", .needs = "kappa_hi and worst must not both be NULL", .plan = true,
+                            .n_scen = n_scen, .params = params, .per = per_instance != 0, .quantity = BAL_MARGIN_GROUPS, .kappa_max = kappa_max,
+                            .n_grp = n_grp, .group_mask = group_mask, .mu_base = mu_base, .out = kappa_hi, .kappa_lo = kappa_lo, .iters = iters,
+                            .worst = worst, .worst_knot = worst_knot});
+}
+
+int upr_batch_speed_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double s_max, double* speed,
+                                  double* z, double* y, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_speed_margin_points", .needs = "x, params and speed must not be NULL", .n = n, .x = x, .n_scen = n_scen,
+                            .params = params, .per = per_point != 0, .quantity = BAL_SPEED, .s_max = s_max, .out = speed, .z = z, .y = y, .iters = iters});
+}
+
+int upr_batch_speed_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double s_max, double* speed, int* iters,
+                                double* window, int* knot, double* limit) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_speed_margin_plan", .needs = "speed and window must not both be NULL", .plan = true, .n_scen = n_scen,
+                            .params = params, .per = per_instance != 0, .quantity = BAL_SPEED, .s_max = s_max, .limit = limit, .out = speed, .iters = iters,
+                            .worst = window, .worst_knot = knot});
+}
+
+int upr_batch_path_accel_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, double d_max, double speed,
+                                       double* accel, double* z, double* y, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_path_accel_margin_points", .needs = "x, params and accel must not be NULL", .n = n, .x = x, .n_scen = n_scen,
+                            .params = params, .per = per_point != 0, .quantity = BAL_PATHACC, .d_max = d_max, .speed = speed, .out = accel, .z = z, .y = y,
+                            .iters = iters});
+}
+
+int upr_batch_path_accel_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, double d_max, double speed, double* accel, int* iters,
+                                     double* window, int* knot, double* limit) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_path_accel_margin_plan", .needs = "accel and window must not both be NULL", .plan = true, .n_scen = n_scen,
+                            .params = params, .per = per_instance != 0, .quantity = BAL_PATHACC, .limit = limit, .d_max = d_max, .speed = speed, .out = accel,
+                            .iters = iters, .worst = window, .worst_knot = knot});
+}
+
+int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, int start_level, int end_level,
+                          int common, int boxes, double* duration, int* level, int* reach, unsigned* edges, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_retime_plan", .needs = "duration and level must not both be NULL", .plan = true, .n_scen = n_scen, .params = params,
+                            .per = per_instance != 0, .quantity = BAL_RETIME, .speeds = speeds, .n_lvl = n_lvl, .start = start_level, .end = end_level,
+                            .common = common != 0, .boxes = boxes != 0, .level = level, .reach = reach, .edges = edges, .out = duration, .iters = iters});
+}
+
+double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }
+
+}  // extern "C"

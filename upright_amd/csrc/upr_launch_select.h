@@ -1,6 +1,6 @@
 // upr_launch_select.h -- which linearisation kernel and which line-search kernel a handle runs, decided ONCE (upr_batch_create)
 // and kept as a value, as upr_qp_select.h does for the QP kernel.  Everything here is host arithmetic on the problem, its
-// dimensions and the knobs; the only per-launch quantity is the grid.  upr_api.hip resolves a choice to a kernel by expanding the
+// dimensions and the knobs; the only per-launch quantity is the grid.  upr_api_launch.hip resolves a choice to a kernel by expanding the
 // lists below, and the host emulation under tests/emu compiles this file with g++ to run the same rules.  (It is not part of a
 // kernel's source: the run-time instantiation's cache key does not hash it.)
 #pragma once
