@@ -9,7 +9,8 @@ Per case, on the device's own linearisation records:
   * fused gains against the dense reference K_ref (tests/fb_check.py) at the point the device exported, per knot and block, FB_TOL;
   * UPR_FB_FUSED = 0: the gather kernel (feedback_kernel of upr_api.hip, source kind 3) against K_ref, FB_TOL.
 Two more cases run the headline shape on the generic and on the second-structure QP kernel (UPR_QP_KERNEL = 1, 2): source kinds 1 and
-2 of the gather kernel against K_ref at the point the same kernel exported.  The run-time instantiated case runs in a fresh child
+2 of the gather kernel against K_ref at the point the same kernel exported; four more (KIND_CASES) do the same on the dice under both
+kinds and, under kind 1, on the eight-corner arrangement and on the headline with collision rows.  The run-time instantiated case runs in a fresh child
 process (measure_in_child: the library keeps such an instantiation per process)."""
 import copy
 import json
@@ -187,18 +188,40 @@ def test_gather_kernel_source_kinds_of_the_other_qp_kernels(kind, monkeypatch):
     """UPR_QP_KERNEL = 1 (generic kernel: source kind 1) and 2 (second structure: kind 2) on the headline shape: the gather kernel forms
     the jerk rows from V_k and the inverse factor of H_jj there.  Point and gains come from the same kernel, K_IT and K_IT + 1
     iterations; prints a (float64 reference vs its extended-precision twin) and b (device gains vs twin) on instance 0."""
+    _kind_screen(kind, RUN_TIME_HEADLINE, KIND_NAME[kind], KIND_TOL[kind][0], monkeypatch)
+
+
+def _kind_screen(kind, cfg, name, tol, monkeypatch):
     monkeypatch.setenv("UPR_QP_KERNEL", kind)
-    c = fb_case(RUN_TIME_HEADLINE)
+    c = fb_case(cfg)
     P, B = c["P"], c["B"]
-    sol, pairs, lin = exported_point(c, KIND_NAME[kind], None)
-    K = device_gains(c, KIND_NAME[kind], None)
+    sol, pairs, lin = exported_point(c, name, None)
+    K = device_gains(c, name, None)
     Kref = [reference_gains(P, lin[b], sol[b], pairs[b], c["bp"][b])[0] for b in range(B)]
     Kx = reference_gains(P, lin[0], sol[0], pairs[0], c["bp"][0], extended=True)[0]
     a, bb = fb_check.block_errors(Kref[0], Kx, P.nq).max(), fb_check.block_errors(K[0], Kx, P.nq).max()
     err = _against_reference(c, K, Kref)
-    tol = KIND_TOL[kind][0]
-    print("fb screen UPR_QP_KERNEL=%s: a %.2e  b %.2e  worst instance %.2e (threshold %.1e)" % (kind, a, bb, err, tol))
+    print("fb screen UPR_QP_KERNEL=%s %s [%s]: a %.2e  b %.2e  worst instance %.2e (threshold %.1e)" % (kind, _ids(cfg), name, a, bb, err, tol))
     assert tol <= CAP and err < tol, (err, tol)
+
+
+# The same screen behind the generic kernel and the second structure on shapes beyond the headline's: two bodies with shared contacts (a
+# dense 12 x 12 inverse Schur factor; kinds 1 and 2), the eight-corner frictionless arrangement with softened rows and per-instance
+# inertial parameters (eight diagonal blocks of Lsi, the generic kernel's 512-lane form) and hard collision rows.
+# (kind, case of the QP screen's table) -> (kernel that has to run, threshold = 10 max(a, b), a, b as in KIND_TOL, measured on the device run)
+DICE, ROBUST, ROWS = (9, 2, 8, 3, 20, False, False, True), (9, 8, 32, 1, 20, False, True, False), (9, 1, 4, 3, 20, True, False, False)
+KIND_CASES = {
+    ("1", DICE): ("upr_qp_kernel<256>", 3.4e-8, 3.03e-9, 3.37e-9),                                # worst instance 4.07e-9
+    ("2", DICE): ("upr_qp2_kernel<upr_qp2_dims<9, 2, 8, 3>, 128>", 3.1e-8, 3.02e-9, 2.93e-9),     # worst instance 2.25e-9
+    ("1", ROBUST): ("upr_qp_kernel<512>", 2.0e-8, 1.96e-9, 1.00e-9),                              # worst instance 2.52e-9
+    ("1", ROWS): ("upr_qp_kernel<256>", 4.2e-8, 3.39e-9, 4.14e-9),                                # worst instance 3.77e-9
+}
+
+
+@pytest.mark.parametrize("kind,cfg", list(KIND_CASES), ids=["%s-%s" % (k, _ids(c)) for k, c in KIND_CASES])
+def test_gather_kernel_source_kinds_on_more_shapes(kind, cfg, monkeypatch):
+    name, tol, _, _ = KIND_CASES[(kind, cfg)]
+    _kind_screen(kind, cfg, name, tol, monkeypatch)
 
 
 # ---- policy evaluation at its edges ---------------------------------------------------------------------------------------------------------

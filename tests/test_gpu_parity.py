@@ -145,13 +145,18 @@ def test_qp_kernel_vs_host_emulation(arrangements, kernel, nt, monkeypatch):
     """Race / indexing screen: the SAME kernel source compiled for the host (tests/emu, one thread per
     workgroup) is fed the GPU's own linearisation records, so any difference beyond summation order is
     a synchronisation or indexing defect of the GPU execution.  Fixed 8 IPM iterations (tol = 0).  (Every instantiation of the
-    production kernel, this case among them, is screened at the one it ran: tests/test_gpu_qp_screen.py.)"""
+    production kernel, this case among them, is screened at the one it ran: tests/test_gpu_qp_screen.py; the other two structures at
+    every shape and lane count: tests/test_gpu_qp_fallback_screen.py.)  UPR_QP_NT sets the lanes of the second structure and of the
+    headline instantiation; the generic kernel takes its own from UPR_QP_GENERIC_NT."""
     monkeypatch.setenv("UPR_QP_KERNEL", kernel)
-    monkeypatch.setenv("UPR_QP_NT", nt)
+    monkeypatch.setenv("UPR_QP_GENERIC_NT" if kernel == "1" else "UPR_QP_NT", nt)
+    ran = {"1": "upr_qp_kernel<%s>" % nt, "2": "upr_qp2_kernel<upr_qp2_dims<9, 1, 4, 3>, %s>" % nt,
+           "3": "upr_qp3_kernel<upr_qp3_cfg<9, 1, 4, 3, 20, %s, false, false, false>>" % nt}[kernel]
     B = 6
     P, x0, way = _setup(arrangements, B, seed=13, qp_tol=0.0, qp_iter_max=8)
     xs0, us0 = stationary_guess(x0, P.N, P.nu)
     mpc = BatchMPC(P, B, way_p=way)
+    assert mpc.kernel_times()["qp_kernel"].replace("  ", " ") == ran, (mpc.kernel_times()["qp_kernel"], ran)
     mpc.set_observation(0.0, x0)
     mpc.set_guess(xs0, us0)
     dxs, dus = mpc.qp_step()
@@ -243,8 +248,10 @@ def test_mpc_solve_one_iteration(arrangements, kernel, nt, monkeypatch):
 @pytest.mark.parametrize("name,offset", [("foam_die2", (-0.5, 0.5, 0.0)), ("box_arch", (-0.5, 0.5, 0.0)), ("blue_cups", (-0.5, 0.5, 0.0))])
 def test_mpc_solve_other_arrangements(arrangements, name, offset):
     """Multi-body arrangements (2 / 3 / 7 bodies, 8 / 16 / 28 contact points: BASELINE config 3's object set):
-    stacked objects couple several bodies through shared contact forces.  foam_die2 runs the compile-time
-    kernel structure, the larger ones the generic (runtime-dimension) QP kernel."""
+    stacked objects couple several bodies through shared contact forces.  All three run a listed instantiation of the
+    production kernel (upr_qp3_list.h: the dense two- and three-body entries, the seven-cup star) -- without collision rows the
+    three-body problem takes the entry that has them compiled in; the generic (runtime-dimension) kernel ran the larger two
+    until the list grew."""
     B = 3
     P = thing_problem(arrangements[name])
     x0 = level_tray_states(B, seed=17)
