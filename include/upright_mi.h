@@ -517,8 +517,34 @@ int upr_batch_path_accel_margin_plan(upr_batch* h, int n_scen, const double* par
  *   copied; duration and level must not both be NULL.  Scratch, timing and the state of the handle as the friction margin above. */
 int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, int start_level,
                           int end_level, int common, int boxes, double* duration, int* level, int* reach, unsigned* edges, int* iters);
-/* device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin or retiming
- * on the handle, HIP events around them (copies excluded) */
+/* ------------------------------------------------------------------------------------------------
+ * Disturbance margin (upright_amd/csrc/upr_disturb.h): how much tray acceleration the plan did not choose a state absorbs along given
+ * directions with the objects still balanced.  dirs[n_dir][6] holds rows u = (u_alpha, u_a), rad/s^2 and m/s^2 per unit r, 1 <= n_dir
+ * <= 32, every entry finite, no row all zero; frame 0: world, the frame the state's omega, alpha and a_ee are in; frame 1: the tray
+ * frame, u_world = C_we u_tray for both halves with the state's own C_we.  The state displaced by r along u has (alpha + r u_alpha,
+ * a_ee + r u_a); b(r) = b(0) + r b_u and A does not depend on r, so the accepted r form one interval.  The rule, the grid r(k) =
+ * r_max (k - 2^31) 2^-31 and the algorithm are the path-acceleration margin's (its special case u = (omega, v_ee), speed 1).
+ *       reach[4]  r_lo, r_lo_out, r_hi, r_hi_out with the conventions of accel[4] above (open ends -inf / +inf; no r accepted: +inf,
+ *                 -r_max, -inf, r_max; a bisected end has |in - out| = r_max 2^-31).  -r_lo is what the state absorbs along -u, r_hi
+ *                 what it absorbs along +u; 0 in [r_lo, r_hi] iff the state is balanced.
+ *       z[2], y[2], iters   as the path-acceleration margin's.
+ *   The layouts are direction-major.  upr_batch_disturbance_margin_points: reach[n_dir][n][n_scen][4], z[n_dir][n][n_scen][2][ncol] or
+ *       NULL, y[n_dir][n][n_scen][2][6 nb] or NULL, iters[n_dir][n][n_scen] or NULL.  Host pointers.
+ *   upr_batch_disturbance_margin_plan  the knots of the current plan on the device: reach[n_dir][B][N+1][n_scen][4] or NULL, iters or
+ *       NULL; window[n_dir][B][n_scen][2] or NULL: per direction the largest r_lo and the smallest r_hi over the knots, knot[n_dir][B]
+ *       [n_scen][2] (or NULL) the first knot attaining each; radius[B][n_scen] or NULL: min over directions of min(-window_lo,
+ *       window_hi), the largest r every knot absorbs along every +-u given -- negative when some knot is not balanced, -inf when some
+ *       job accepts nothing; binding[B][n_scen][3] or NULL: (direction, sign -1 | +1, knot) of the end that attains radius, directions
+ *       in ascending order, the lower end before the upper, the first end wins ties.  reach, window and radius must not all be NULL.
+ *   r_max must be finite and > 0.  Scratch, timing and the state of the handle as the friction margin above. */
+int upr_batch_disturbance_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point,
+                                        int n_dir, const double* dirs, int frame, double r_max,
+                                        double* reach, double* z, double* y, int* iters);
+int upr_batch_disturbance_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance,
+                                      int n_dir, const double* dirs, int frame, double r_max,
+                                      double* reach, int* iters, double* window, int* knot, double* radius, int* binding);
+/* device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin, retiming
+ * or disturbance margin on the handle, HIP events around them (copies excluded) */
 double upr_batch_balance_ms(upr_batch* h);
 
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):

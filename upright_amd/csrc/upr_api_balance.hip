@@ -1,6 +1,6 @@
 // upr_api_balance.hip -- the balance family of libupright_mi.so (include/upright_mi.h): request, validation, launcher and the
-// fifteen entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan with upr_batch_balance_ms.  The one unit that includes
-// upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h and upr_retime.h: their kernels are defined here and nowhere else.
+// seventeen entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan with upr_batch_balance_ms.  The one unit that includes
+// upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h and upr_disturb.h: their kernels are defined here and nowhere else.
 // What crosses to upr_api.hip (upr_handle.h): upr_bal_resolve, the part of upr_batch_create that fills the handle's choice of form;
 // from there it takes upr_fail.  The family reads and writes the handle's bal, bal_buf / bal_cap, bal_ev and bal_ms, nothing else.
 #include "upr_handle.h"
@@ -12,6 +12,7 @@
 #include "upr_speed.h"
 #include "upr_pathacc.h"
 #include "upr_retime.h"
+#include "upr_disturb.h"
 
 // the form of a handle's balance family (UPR_BAL_FORM=0: the wave form for the one-body shapes too; tests)
 void upr_bal_resolve(upr_batch* h) {
@@ -24,7 +25,7 @@ void upr_bal_resolve(upr_batch* h) {
 
 namespace {
 
-// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h): the fifteen entry points end here, in balance_call.  An entry fills a REQUEST, which
+// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h): the seventeen entry points end here, in balance_call.  An entry fills a REQUEST, which
 // names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
 // go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
 // the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
@@ -34,8 +35,9 @@ namespace {
 // that serves nothing else and only grows (bal_buf): a call in the steady state allocates and frees nothing.
 enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
 // the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h) | the
-// path-acceleration margin (upr_pathacc.h) | the retiming of a plan on a speed lattice (upr_retime.h)
-enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5 };
+// path-acceleration margin (upr_pathacc.h) | the retiming of a plan on a speed lattice (upr_retime.h) | the disturbance margin
+// (upr_disturb.h)
+enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5, BAL_DISTURB = 6 };
 struct bal_request {
     const char* who = "";     // the entry, as its messages name it
     const char* needs = "";   // ... and what they say about its required pointers
@@ -61,6 +63,10 @@ struct bal_request {
     // with common; level [..][N + 1], reach [..][2]; edges [B][n_scen][N][n_lvl] and iters, one per mask row, stay per scenario
     const double* speeds = nullptr; int n_lvl = 0, start = -1, end = -1; bool common = false, boxes = true;
     int *level = nullptr, *reach = nullptr; unsigned* edges = nullptr;
+    // the disturbance margin: dirs [n_dir][6] = (u_alpha, u_a) in the world (frame 0) or the tray frame (1), the range [-r_max, r_max];
+    // out is reach, four doubles per job, and every per-job output gains a LEADING [n_dir]; worst / worst_knot ([n_dir][B][n_scen][2];
+    // plan) the window per direction, radius [B][n_scen] and binding [B][n_scen][3] the reduction over the directions
+    const double* dirs = nullptr; int n_dir = 0, frame = 0; double r_max = 0.0; double* radius = nullptr; int* binding = nullptr;
     // the answers on the host; all but the required ones may be NULL.  worst / worst_knot ([B][n_scen][n_grp]; plan, per group): the
     // largest kappa_hi over the knots of an instance, reduced on the device; out may then be NULL and kappa_hi stays on the device
     double* out = nullptr;   // rho | kappa_hi
@@ -106,7 +112,7 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
         return upr_fail("path-acceleration margin: d_max must be finite and > 0, speed finite and >= 0");
     if (r.quantity == BAL_MARGIN_GROUPS && balance_check_groups(h, r.n_grp, r.group_mask)) return 1;
     if (!r.plan && r.n <= 0) return 2;
-    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst && !r.level)) return refuse(r.needs);
+    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst && !r.level && !r.radius)) return refuse(r.needs);
     if (r.plan && !r.params) {
         if (r.n_scen != 1) return refuse("params == NULL needs n_scen == 1 (every instance's own body parameters)");
     } else if (r.n_scen < 1) return refuse("n_scen must be >= 1");
@@ -123,38 +129,53 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
         if (r.start < -1 || r.start >= r.n_lvl || r.end < -1 || r.end >= r.n_lvl) return upr_fail("retime: start and end must be -1 or a level index");
         if (n * r.n_scen * r.n_lvl > (1ll << 36)) return upr_fail("balance check: too many points");   // (the jobs: a mask row each)
     }
+    if (r.quantity == BAL_DISTURB) {
+        if (!(r.r_max > 0) || !std::isfinite(r.r_max)) return upr_fail("disturbance margin: r_max must be finite and > 0");
+        bool ok = r.dirs && r.n_dir >= 1 && r.n_dir <= UPR_DST_MAX_DIRS;
+        for (int k = 0; ok && k < r.n_dir; ++k) {
+            bool any = false;
+            for (int i = 0; ok && i < 6; ++i) { ok = std::isfinite(r.dirs[6 * k + i]); any = any || r.dirs[6 * k + i] != 0.0; }
+            ok = ok && any;
+        }
+        if (!ok) return upr_fail("disturbance margin: dirs must be 1 .. 32 finite non-zero directions");
+        if (r.frame != 0 && r.frame != 1) return upr_fail("disturbance margin: frame must be 0 (world) or 1 (tray)");
+        if (n * r.n_scen * r.n_dir > (1ll << 36)) return upr_fail("balance check: too many points");   // (the jobs: one per direction)
+    }
     return 0;
 }
 
 // form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
-// group, the speed margin, the path-acceleration margin, the edge masks of the retiming.  Every kernel takes (its record, upr_bal_dims,
-// long long jobs); the record is upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the groups, upr_spd_args for the
-// speed margin, upr_pac_args for the path-acceleration margin and upr_ret_args for the retiming.
-const void* const bal_kernels[2][8] = {
+// group, the speed margin, the path-acceleration margin, the edge masks of the retiming, the disturbance margin.  Every kernel takes
+// (its record, upr_bal_dims, long long jobs); the record is upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the
+// groups, upr_spd_args for the speed margin, upr_pac_args for the path-acceleration margin, upr_ret_args for the retiming and
+// upr_dst_args for the disturbance margin.
+const void* const bal_kernels[2][9] = {
     /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
                     (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel,
-                    (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel},
+                    (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel, (const void*)upr_bal_disturb1_kernel},
     /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
                     (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel,
-                    (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel}};
+                    (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel, (const void*)upr_bal_disturb_kernel}};
 struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
 
 int balance_launch(upr_batch* h, const bal_request& r) {
     const upr_dims& d = h->d;
     upr_bal_dims L = h->bal.L;
-    const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, speed = r.quantity == BAL_SPEED || pathacc;   // (speed: the four-double layout)
+    const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, disturb = r.quantity == BAL_DISTURB;
+    const bool speed = r.quantity == BAL_SPEED || pathacc || disturb;   // (speed: the four-double layout)
     const bool retime = r.quantity == BAL_RETIME;
     const bool margin = r.quantity != BAL_RHO && !speed && !retime, groups = r.quantity == BAL_MARGIN_GROUPS;
     // (the retiming: a job is a mask row, (instance, scenario, segment, level); nplans outputs of the path kernel)
-    const long long n = bal_points(h, r), njobs = retime ? (long long)h->B * r.n_scen * d.N * r.n_lvl : n * r.n_scen, ng = r.n_grp, nout = njobs * ng;
+    const long long n = bal_points(h, r), njobs = retime ? (long long)h->B * r.n_scen * d.N * r.n_lvl : n * r.n_scen, ng = disturb ? r.n_dir : r.n_grp, nout = njobs * ng;
     const long long nplans = retime ? (long long)h->B * (r.common ? 1 : r.n_scen) : 0;
-    const bool want_worst = r.worst || r.worst_knot;
-    const long long nworst = want_worst ? (long long)h->B * r.n_scen * (speed ? 2 : ng) : 0;
+    // (the disturbance margin: njobs the jobs of one direction, ng the directions -- the groups' place, but the leading axis)
+    const bool want_worst = r.worst || r.worst_knot || r.radius || r.binding;
+    const long long nworst = want_worst ? (long long)h->B * r.n_scen * (disturb ? 2 * ng : speed ? 2 : ng) : 0;
     const size_t per_out = speed ? 4 : 1, ends = speed ? 2 : 1;   // doubles of `out` and certificates per job
     const double* scale_host = groups ? r.mu_base : r.mu_scale;
     const size_t scale_count = (size_t)r.n_scen * ((groups || r.scale == BAL_MU_CONTACT) ? d.nc : 1);
     // the scratch block, region by region, with what goes into a region before the kernels (from) and out of it after them (to)
-    bal_copy up[4], down[8];
+    bal_copy up[4], down[10];
     int nup = 0, ndown = 0; size_t total = 0;
     auto region = [&](size_t bytes, bool wanted, const void* from, void* to) {
         const size_t o = bal_take(total, bytes, wanted);
@@ -181,6 +202,9 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const size_t o_arg = region((size_t)nplans * d.N * r.n_lvl, retime, nullptr, nullptr);
     const size_t o_lvl = region(sizeof(int) * nplans * (d.N + 1), retime, nullptr, r.level);
     const size_t o_rch = region(sizeof(int) * nplans * 2, retime && r.reach, nullptr, r.reach);
+    const size_t o_dir = region(sizeof(double) * ng * 6, disturb, r.dirs, nullptr);
+    const size_t o_rad = region(sizeof(double) * h->B * r.n_scen, disturb && r.radius, nullptr, r.radius);
+    const size_t o_bnd = region(sizeof(int) * h->B * r.n_scen * 3, disturb && r.binding, nullptr, r.binding);
     if (balance_scratch(h, total)) return 1;
     char* base = (char*)h->bal_buf;
     for (int i = 0; i < nup; ++i) UPR_HIP(hipMemcpyAsync(base + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, h->stream));
@@ -206,11 +230,16 @@ int balance_launch(upr_batch* h, const bal_request& r) {
         M.kappa_lo = r.kappa_lo ? (double*)(base + o_lo) : nullptr; M.y = r.y ? (double*)(base + o_y) : nullptr;
     }
     upr_spd_args S;
-    if (speed && !pathacc) { S.J = A; S.J.rho = nullptr; S.s_max = r.s_max; S.speed = drho; S.y = r.y ? (double*)(base + o_y) : nullptr; }
+    if (speed && !pathacc && !disturb) { S.J = A; S.J.rho = nullptr; S.s_max = r.s_max; S.speed = drho; S.y = r.y ? (double*)(base + o_y) : nullptr; }
     upr_pac_args C;
     if (pathacc) {
         C.J = A; C.J.rho = nullptr; C.d_max = r.d_max; C.speed = r.speed; C.vee = (const double*)(base + o_vee); C.accel = drho;
         C.y = r.y ? (double*)(base + o_y) : nullptr;
+    }
+    upr_dst_args D;
+    if (disturb) {
+        D.J = A; D.J.rho = nullptr; D.r_max = r.r_max; D.dirs = (const double*)(base + o_dir); D.n_dir = (int)ng; D.frame = r.frame; D.reach = drho;
+        D.y = r.y ? (double*)(base + o_y) : nullptr;
     }
     upr_ret_args T;
     if (retime) {
@@ -222,9 +251,9 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     // lane form: 64 jobs per workgroup, the groups on the y axis.  Wave form: a workgroup is one wave and the jobs (for the groups:
     // job x group) are dealt round robin to a grid that fills the device a few times over (its LDS, at most 26.4 KB, lets six of
     // the largest shape share a CU inside the 160 KiB)
-    long long count = (wave && groups) ? nout : njobs;
+    long long count = (wave && (groups || disturb)) ? nout : njobs;
     const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
-    void* args[] = {retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
+    void* args[] = {disturb ? (void*)&D : retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
     UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
     if (retime) {
         upr_ret_path_args Q;
@@ -232,13 +261,19 @@ int balance_launch(upr_batch* h, const bal_request& r) {
         Q.h = h->P.dt; Q.arg = (unsigned char*)(base + o_arg); Q.duration = drho; Q.level = (int*)(base + o_lvl); Q.reach = r.reach ? (int*)(base + o_rch) : nullptr;
         hipLaunchKernelGGL(upr_bal_retime_path_kernel, dim3((unsigned)(nplans < 16384 ? nplans : 16384)), dim3(64), 0, h->stream, Q, nplans);
         UPR_HIP(hipGetLastError());
+    } else if (disturb && want_worst) {
+        const long long nbs = (long long)h->B * r.n_scen;
+        hipLaunchKernelGGL(upr_bal_disturb_plan_kernel, dim3((unsigned)((nbs + 63) / 64)), dim3(64), 0, h->stream, (const double*)drho, d.N + 1, r.n_scen,
+                           (int)ng, nbs, (double*)(base + o_w), (int*)(base + o_wk), r.radius ? (double*)(base + o_rad) : nullptr,
+                           r.binding ? (int*)(base + o_bnd) : nullptr);
+        UPR_HIP(hipGetLastError());
     } else if (pathacc && (want_worst || r.limit)) {
         const long long lanes = nworst + (r.limit ? h->B : 0);
         hipLaunchKernelGGL(upr_bal_pathacc_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
                            d.N + 1, r.n_scen, nworst, h->B, d.nx, r.speed, (const double*)h->xs, (double*)(base + o_w),
                            r.worst_knot ? (int*)(base + o_wk) : nullptr, r.limit ? (double*)(base + o_lim) : nullptr);
         UPR_HIP(hipGetLastError());
-    } else if (speed && (want_worst || r.limit)) {
+    } else if (speed && !disturb && (want_worst || r.limit)) {
         const long long lanes = nworst + (r.limit ? h->B : 0);
         hipLaunchKernelGGL(upr_bal_speed_plan_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, h->stream, (const upr_problem*)h->dP, (const double*)drho,
                            d.N + 1, r.n_scen, nworst, h->B, d.nx, d.nu, (const double*)h->xs, (const double*)h->us, (double*)(base + o_w),
@@ -372,6 +407,23 @@ int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int pe
     return balance_call(h, {.who = "upr_batch_retime_plan", .needs = "duration and level must not both be NULL", .plan = true, .n_scen = n_scen, .params = params,
                             .per = per_instance != 0, .quantity = BAL_RETIME, .speeds = speeds, .n_lvl = n_lvl, .start = start_level, .end = end_level,
                             .common = common != 0, .boxes = boxes != 0, .level = level, .reach = reach, .edges = edges, .out = duration, .iters = iters});
+}
+
+int upr_batch_disturbance_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, int n_dir, const double* dirs,
+                                        int frame, double r_max, double* reach, double* z, double* y, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_disturbance_margin_points", .needs = "x, params and reach must not be NULL", .n = n, .x = x, .n_scen = n_scen,
+                            .params = params, .per = per_point != 0, .quantity = BAL_DISTURB, .dirs = dirs, .n_dir = n_dir, .frame = frame, .r_max = r_max,
+                            .out = reach, .z = z, .y = y, .iters = iters});
+}
+
+int upr_batch_disturbance_margin_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_dir, const double* dirs, int frame, double r_max,
+                                      double* reach, int* iters, double* window, int* knot, double* radius, int* binding) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_disturbance_margin_plan", .needs = "reach, window and radius must not all be NULL", .plan = true,
+                            .n_scen = n_scen, .params = params, .per = per_instance != 0, .quantity = BAL_DISTURB, .dirs = dirs, .n_dir = n_dir,
+                            .frame = frame, .r_max = r_max, .radius = radius, .binding = binding, .out = reach, .iters = iters, .worst = window,
+                            .worst_knot = knot});
 }
 
 double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }

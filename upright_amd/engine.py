@@ -574,6 +574,65 @@ class BatchMPC:
             return w, knot, limit
         return self._asked_for(acc[..., 0::2].copy(), acc[..., 1::2].copy() if want_out else None, iters)
 
+    @staticmethod
+    def _dirs(dirs, frame):
+        """dirs (n_dir, 6) contiguous, n_dir, frame 0 | 1"""
+        dirs = cont(dirs).reshape(-1, 6)
+        if frame not in ("world", "tray", 0, 1):
+            raise ValueError("frame must be 'world' or 'tray'")
+        return dirs, dirs.shape[0], (1 if frame in ("tray", 1) else 0)
+
+    def disturbance_margin(self, x, params, dirs, r_max=8.0, frame="tray", want_out=False, want_z=False, want_y=False, want_iters=False):
+        """r (n_dir, n, n_scen, 2) = (r_lo, r_hi): the interval of unplanned tray acceleration along each direction of dirs that the
+        robot states x (n, 3 nq) absorb with the objects balanced under the inertial parameters params (layouts of balance_check;
+        upr_batch_disturbance_margin_points).  dirs (n_dir, 6): rows u = (u_alpha, u_a), the angular (rad/s^2) and linear (m/s^2)
+        acceleration of the tray per unit r, 1 <= n_dir <= 32, finite, no row all zero; frame "tray": in the tray's own frame (rotated
+        by every state's C_we), "world": in the world frame.  The state displaced by r along u has the end-effector accelerations
+        (alpha + r u_alpha, a_ee + r u_a); r counts as balanced when the distance rho there is <= 1e-8 max(|b|, 1), the rule of
+        friction_margin.  -r_lo is what the state absorbs along -u, r_hi what it absorbs along +u (r_max: balanced up to r_max);
+        r_lo <= 0 <= r_hi iff the state itself is balanced; (inf, -inf): no r in [-r_max, r_max] balances it.  Both ends are the
+        accepted, conservative side of a bracket of width r_max 2^-31.  path_accel_margin at speed 1 is the direction (omega, v_ee) in
+        the world frame.  r_max must be finite and > 0.
+
+        Returns r alone or the tuple (r, out, z, y, iters) restricted to what was asked for, every array with the leading direction
+        axis: out (n_dir, n, n_scen, 2) = (r_lo_out, r_hi_out) the rejected neighbours of the two ends (-inf below an r_lo of -r_max,
+        inf above an r_hi of r_max; (-r_max, r_max) where no r is accepted); z (n_dir, n, n_scen, 2, ncol) >= 0 the generator
+        multipliers at r_lo and at r_hi; y (n_dir, n, n_scen, 2, 6 nb) the residuals at r_lo_out and r_hi_out, separating directions;
+        iters (n_dir, n, n_scen) the least-squares solves over all evaluations (at most 3 + 3 * 32 of them)."""
+        x, n, params, n_scen, per_point = self._points_args(x, params)
+        dirs, n_dir, frame = self._dirs(dirs, frame)
+        reach, z, y, iters = self._outputs((n_dir, n, n_scen), (True, (4,), F8), (want_z, (2, self.balance_columns), F8), (want_y, (2, self.ne), F8),
+                                           (want_iters, (), I4))
+        check(self._lib.upr_batch_disturbance_margin_points(self._h, n, ptr(x), n_scen, ptr(params), per_point, n_dir, ptr(dirs), frame, float(r_max),
+                                                            ptr(reach), ptr(z), ptr(y), iptr(iters)))
+        return self._asked_for(reach[..., 0::2].copy(), reach[..., 1::2].copy() if want_out else None, z, y, iters)
+
+    def disturbance_margin_plan(self, dirs, params=None, r_max=8.0, frame="tray", want_out=False, want_iters=False, window=False, radius=False):
+        """r (n_dir, B, N + 1, n_scen, 2) = (r_lo, r_hi) at the knots of the current plan, evaluated where they lie on the device
+        (upr_batch_disturbance_margin_plan); params as in balance_check_plan, the quantity as in disturbance_margin.  With want_out /
+        want_iters the tuple (r, out, iters) restricted to what was asked for.
+
+        window=True: instead of r per knot the pair (window (n_dir, B, n_scen, 2), knot (n_dir, B, n_scen, 2)) -- per direction the
+        largest r_lo and the smallest r_hi over the knots of every instance and the first knot that attains each.  radius=True: the
+        pair (radius (B, n_scen), binding (B, n_scen, 3)) -- radius = min over directions of min(-window_lo, window_hi), the largest
+        r that every knot of the plan absorbs along every +-u given (negative when some knot is not balanced, -inf when some knot and
+        direction accept nothing), binding = (direction, sign -1 | +1, knot) of the end that attains it (directions in ascending
+        order, the lower end before the upper, the first end wins ties).  With both: (window, knot, radius, binding).  Reduced on the
+        device, only these are downloaded; want_out / want_iters are not available with them."""
+        n_scen, per_instance, params = self._plan_params(params)
+        dirs, n_dir, frame = self._dirs(dirs, frame)
+        reduced = window or radius
+        if reduced and (want_out or want_iters):
+            raise ValueError("window=True / radius=True return the reductions alone")
+        reach, iters = self._outputs((n_dir, self.B, self.N + 1, n_scen), (not reduced, (4,), F8), (want_iters, (), I4))
+        w, knot = self._outputs((n_dir, self.B, n_scen, 2), (window, (), F8), (window, (), I4))
+        rad, bind = self._outputs((self.B, n_scen), (radius, (), F8), (radius, (3,), I4))
+        check(self._lib.upr_batch_disturbance_margin_plan(self._h, n_scen, ptr(params), per_instance, n_dir, ptr(dirs), frame, float(r_max), ptr(reach),
+                                                          iptr(iters), ptr(w), iptr(knot), ptr(rad), iptr(bind)))
+        if reduced:
+            return self._asked_for(w, knot, rad, bind)
+        return self._asked_for(reach[..., 0::2].copy(), reach[..., 1::2].copy() if want_out else None, iters)
+
     def retime_plan(self, speeds, params=None, start=None, end=None, common=False, boxes=True, want_reach=False, want_edges=False, want_iters=False):
         """(duration, level): the fastest time law on the lattice `speeds` that replays the geometric path of the current plan with the
         objects balanced at every knot (upr_batch_retime_plan), where speed_margin_plan could only offer one uniform factor.  speeds
@@ -645,8 +704,8 @@ class BatchMPC:
         return t, side(x[..., :-1, :], s0), side(x[..., 1:, :], s1)
 
     def balance_ms(self):
-        """Device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin or retiming
-        (HIP events around them)."""
+        """Device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin, retiming
+        or disturbance margin (HIP events around them)."""
         return float(self._lib.upr_batch_balance_ms(self._h))
 
     def balance_forces(self, z):
