@@ -1,6 +1,7 @@
 // upr_api_balance.hip -- the balance family of libupright_mi.so (include/upright_mi.h): request, validation, launcher and the
-// seventeen entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan with upr_batch_balance_ms.  The one unit that includes
-// upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h and upr_disturb.h: their kernels are defined here and nowhere else.
+// eighteen entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan* with upr_batch_balance_ms.  The one unit that includes
+// upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h and upr_retime_rsv.h: their kernels are defined here
+// and nowhere else.
 // What crosses to upr_api.hip (upr_handle.h): upr_bal_resolve, the part of upr_batch_create that fills the handle's choice of form;
 // from there it takes upr_fail.  The family reads and writes the handle's bal, bal_buf / bal_cap, bal_ev and bal_ms, nothing else.
 #include "upr_handle.h"
@@ -13,6 +14,7 @@
 #include "upr_pathacc.h"
 #include "upr_retime.h"
 #include "upr_disturb.h"
+#include "upr_retime_rsv.h"
 
 // the form of a handle's balance family (UPR_BAL_FORM=0: the wave form for the one-body shapes too; tests)
 void upr_bal_resolve(upr_batch* h) {
@@ -25,7 +27,7 @@ void upr_bal_resolve(upr_batch* h) {
 
 namespace {
 
-// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h): the seventeen entry points end here, in balance_call.  An entry fills a REQUEST, which
+// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h, upr_retime_rsv.h): the eighteen entry points end here, in balance_call.  An entry fills a REQUEST, which
 // names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
 // go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
 // the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
@@ -36,8 +38,8 @@ namespace {
 enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
 // the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h) | the
 // path-acceleration margin (upr_pathacc.h) | the retiming of a plan on a speed lattice (upr_retime.h) | the disturbance margin
-// (upr_disturb.h)
-enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5, BAL_DISTURB = 6 };
+// (upr_disturb.h) | the retiming with a reserve (upr_retime_rsv.h)
+enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5, BAL_DISTURB = 6, BAL_RETIME_RSV = 7 };
 struct bal_request {
     const char* who = "";     // the entry, as its messages name it
     const char* needs = "";   // ... and what they say about its required pointers
@@ -67,6 +69,9 @@ struct bal_request {
     // out is reach, four doubles per job, and every per-job output gains a LEADING [n_dir]; worst / worst_knot ([n_dir][B][n_scen][2];
     // plan) the window per direction, radius [B][n_scen] and binding [B][n_scen][3] the reduction over the directions
     const double* dirs = nullptr; int n_dir = 0, frame = 0; double r_max = 0.0; double* radius = nullptr; int* binding = nullptr;
+    // the retiming with a reserve: the retiming's fields, dirs / n_dir / frame as the disturbance margin's and the reserve r >= 0 every
+    // end state must absorb along every +-u; the outputs and their layouts are the retiming's
+    double reserve = 0.0;
     // the answers on the host; all but the required ones may be NULL.  worst / worst_knot ([B][n_scen][n_grp]; plan, per group): the
     // largest kappa_hi over the knots of an instance, reduced on the device; out may then be NULL and kappa_hi stays on the device
     double* out = nullptr;   // rho | kappa_hi
@@ -122,7 +127,7 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
     if (balance_check_scales(r.mu_base, (size_t)r.n_scen * d.nc, "mu_base")) return 1;
     const long long n = bal_points(h, r);
     if (n > (1ll << 31) - 64 || n * r.n_scen * r.n_grp > (1ll << 36)) return upr_fail("balance check: too many points");
-    if (r.quantity == BAL_RETIME) {
+    if (r.quantity == BAL_RETIME || r.quantity == BAL_RETIME_RSV) {
         bool ok = r.speeds && r.n_lvl >= 1 && r.n_lvl <= UPR_RET_MAX_LEVELS;
         for (int m = 0; ok && m < r.n_lvl; ++m) ok = std::isfinite(r.speeds[m]) && r.speeds[m] >= 0 && (m == 0 || r.speeds[m] > r.speeds[m - 1]);
         if (!ok) return upr_fail("retime: speeds must be 1 .. 32 finite values >= 0 in strictly increasing order");
@@ -141,21 +146,34 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
         if (r.frame != 0 && r.frame != 1) return upr_fail("disturbance margin: frame must be 0 (world) or 1 (tray)");
         if (n * r.n_scen * r.n_dir > (1ll << 36)) return upr_fail("balance check: too many points");   // (the jobs: one per direction)
     }
+    if (r.quantity == BAL_RETIME_RSV) {
+        if (!(r.reserve >= 0) || !std::isfinite(r.reserve)) return upr_fail("retime: reserve must be finite and >= 0");
+        bool ok = r.dirs && r.n_dir >= 1 && r.n_dir <= UPR_DST_MAX_DIRS;
+        for (int k = 0; ok && k < r.n_dir; ++k) {
+            bool any = false;
+            for (int i = 0; ok && i < 6; ++i) { ok = std::isfinite(r.dirs[6 * k + i]); any = any || r.dirs[6 * k + i] != 0.0; }
+            ok = ok && any;
+        }
+        if (!ok) return upr_fail("retime: dirs must be 1 .. 32 finite non-zero directions");
+        if (r.frame != 0 && r.frame != 1) return upr_fail("retime: frame must be 0 (world) or 1 (tray)");
+    }
     return 0;
 }
 
 // form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
-// group, the speed margin, the path-acceleration margin, the edge masks of the retiming, the disturbance margin.  Every kernel takes
+// group, the speed margin, the path-acceleration margin, the edge masks of the retiming, the disturbance margin, the edge masks of the retiming with a reserve.  Every kernel takes
 // (its record, upr_bal_dims, long long jobs); the record is upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the
-// groups, upr_spd_args for the speed margin, upr_pac_args for the path-acceleration margin, upr_ret_args for the retiming and
-// upr_dst_args for the disturbance margin.
-const void* const bal_kernels[2][9] = {
+// groups, upr_spd_args for the speed margin, upr_pac_args for the path-acceleration margin, upr_ret_args for the retiming,
+// upr_dst_args for the disturbance margin and upr_ret_rsv_args for the retiming with a reserve.
+const void* const bal_kernels[2][10] = {
     /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
                     (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel,
-                    (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel, (const void*)upr_bal_disturb1_kernel},
+                    (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel, (const void*)upr_bal_disturb1_kernel,
+                    (const void*)upr_bal_retime_rsv1_kernel},
     /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
                     (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel,
-                    (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel, (const void*)upr_bal_disturb_kernel}};
+                    (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel, (const void*)upr_bal_disturb_kernel,
+                    (const void*)upr_bal_retime_rsv_kernel}};
 struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
 
 int balance_launch(upr_batch* h, const bal_request& r) {
@@ -163,7 +181,7 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     upr_bal_dims L = h->bal.L;
     const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, disturb = r.quantity == BAL_DISTURB;
     const bool speed = r.quantity == BAL_SPEED || pathacc || disturb;   // (speed: the four-double layout)
-    const bool retime = r.quantity == BAL_RETIME;
+    const bool reserve = r.quantity == BAL_RETIME_RSV, retime = r.quantity == BAL_RETIME || reserve;   // (retime: what both retimings do)
     const bool margin = r.quantity != BAL_RHO && !speed && !retime, groups = r.quantity == BAL_MARGIN_GROUPS;
     // (the retiming: a job is a mask row, (instance, scenario, segment, level); nplans outputs of the path kernel)
     const long long n = bal_points(h, r), njobs = retime ? (long long)h->B * r.n_scen * d.N * r.n_lvl : n * r.n_scen, ng = disturb ? r.n_dir : r.n_grp, nout = njobs * ng;
@@ -202,7 +220,7 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const size_t o_arg = region((size_t)nplans * d.N * r.n_lvl, retime, nullptr, nullptr);
     const size_t o_lvl = region(sizeof(int) * nplans * (d.N + 1), retime, nullptr, r.level);
     const size_t o_rch = region(sizeof(int) * nplans * 2, retime && r.reach, nullptr, r.reach);
-    const size_t o_dir = region(sizeof(double) * ng * 6, disturb, r.dirs, nullptr);
+    const size_t o_dir = region(sizeof(double) * (reserve ? r.n_dir : ng) * 6, disturb || reserve, r.dirs, nullptr);
     const size_t o_rad = region(sizeof(double) * h->B * r.n_scen, disturb && r.radius, nullptr, r.radius);
     const size_t o_bnd = region(sizeof(int) * h->B * r.n_scen * 3, disturb && r.binding, nullptr, r.binding);
     if (balance_scratch(h, total)) return 1;
@@ -246,6 +264,8 @@ int balance_launch(upr_batch* h, const bal_request& r) {
         T.J = A; T.J.rho = nullptr; T.vee = (const double*)(base + o_vee); T.xs = dx; T.speeds = (const double*)(base + o_spd); T.M = r.n_lvl;
         T.nk = d.N + 1; T.nx = d.nx; T.boxes = r.boxes ? 1 : 0; T.h = h->P.dt; T.edges = (unsigned*)(base + o_edg);
     }
+    upr_ret_rsv_args V;
+    if (reserve) { V.T = T; V.dirs = (const double*)(base + o_dir); V.n_dir = r.n_dir; V.frame = r.frame; V.reserve = r.reserve; }
     upr_grp_args X;
     if (groups) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = r.mu_base ? (const double*)(base + o_mu) : nullptr; }
     // lane form: 64 jobs per workgroup, the groups on the y axis.  Wave form: a workgroup is one wave and the jobs (for the groups:
@@ -253,7 +273,7 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     // the largest shape share a CU inside the 160 KiB)
     long long count = (wave && (groups || disturb)) ? nout : njobs;
     const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
-    void* args[] = {disturb ? (void*)&D : retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
+    void* args[] = {reserve ? (void*)&V : disturb ? (void*)&D : retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
     UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
     if (retime) {
         upr_ret_path_args Q;
@@ -407,6 +427,16 @@ int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int pe
     return balance_call(h, {.who = "upr_batch_retime_plan", .needs = "duration and level must not both be NULL", .plan = true, .n_scen = n_scen, .params = params,
                             .per = per_instance != 0, .quantity = BAL_RETIME, .speeds = speeds, .n_lvl = n_lvl, .start = start_level, .end = end_level,
                             .common = common != 0, .boxes = boxes != 0, .level = level, .reach = reach, .edges = edges, .out = duration, .iters = iters});
+}
+
+int upr_batch_retime_plan_reserve(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, int start_level,
+                                  int end_level, int common, int boxes, int n_dir, const double* dirs, int frame, double reserve, double* duration, int* level,
+                                  int* reach, unsigned* edges, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_retime_plan_reserve", .needs = "duration and level must not both be NULL", .plan = true, .n_scen = n_scen,
+                            .params = params, .per = per_instance != 0, .quantity = BAL_RETIME_RSV, .speeds = speeds, .n_lvl = n_lvl, .start = start_level,
+                            .end = end_level, .common = common != 0, .boxes = boxes != 0, .level = level, .reach = reach, .edges = edges, .dirs = dirs,
+                            .n_dir = n_dir, .frame = frame, .reserve = reserve, .out = duration, .iters = iters});
 }
 
 int upr_batch_disturbance_margin_points(upr_batch* h, int n, const double* x, int n_scen, const double* params, int per_point, int n_dir, const double* dirs,

@@ -633,7 +633,8 @@ class BatchMPC:
             return self._asked_for(w, knot, rad, bind)
         return self._asked_for(reach[..., 0::2].copy(), reach[..., 1::2].copy() if want_out else None, iters)
 
-    def retime_plan(self, speeds, params=None, start=None, end=None, common=False, boxes=True, want_reach=False, want_edges=False, want_iters=False):
+    def retime_plan(self, speeds, params=None, start=None, end=None, common=False, boxes=True, want_reach=False, want_edges=False, want_iters=False,
+                    reserve=None, dirs=None, frame="tray"):
         """(duration, level): the fastest time law on the lattice `speeds` that replays the geometric path of the current plan with the
         objects balanced at every knot (upr_batch_retime_plan), where speed_margin_plan could only offer one uniform factor.  speeds
         (M,): replay speeds s_0 < s_1 < .., finite, >= 0, 1 <= M <= 32.  The law gives knot i the speed speeds[level[i]] and keeps
@@ -667,15 +668,34 @@ class BatchMPC:
             speeds = np.linspace(0.0, 1.5, 13)
             duration, level = mpc.retime_plan(speeds, np.stack(params), common=True, end=0.0)   # (B,), (B, N + 1)
             t, dep, arr = mpc.retimed_states(level, speeds)   # knot times and the states on both sides of every segment
+
+        reserve=r (a number >= 0; upr_batch_retime_plan_reserve): a time-optimal law rides the constraint, its end states absorb about
+        nothing.  With a reserve an end state is accepted only if it is balanced itself and, when r > 0, still balanced when the tray is
+        pushed by +r u and by -r u along every row u = (u_alpha, u_a) of dirs (n_dir, 6) -- the displacement, the frame ("tray" |
+        "world") and the unit of r are disturbance_margin's.  The answer is the fastest law on the lattice that keeps that reserve at
+        every knot; outputs and options as above, iters at most 2 M (1 + 2 n_dir) projections per row.  Between +r u and -r u the
+        whole segment is certified (the cone is convex); nothing is claimed for combinations of directions.  reserve=0 gives the plain
+        law bit for bit; reserve=None (the default) is the plain call and ignores dirs and frame.
+
+            zx = np.array([[0, 0, 0, 0, 0, 1.0], [0, 0, 0, 1.0, 0, 0]])       # the tray's own z and x axes
+            duration, level = mpc.retime_plan(speeds, reserve=0.5, dirs=zx)   # every knot absorbs 0.5 m/s^2 along +-z and +-x
         """
         speeds = cont(speeds).reshape(-1)
         n_scen, per_instance, params = self._plan_params(params)
         lead = (self.B,) if common else (self.B, n_scen)
         dur, level, reach = self._outputs(lead, (True, (), F8), (True, (self.N + 1,), I4), (want_reach, (2,), I4))
         edges, iters = self._outputs((self.B, n_scen, self.N, speeds.size), (want_edges, (), np.uint32), (want_iters, (), I4))
-        check(self._lib.upr_batch_retime_plan(self._h, n_scen, ptr(params), per_instance, int(speeds.size), ptr(speeds), _level_of(speeds, start, "start"),
-                                              _level_of(speeds, end, "end"), int(bool(common)), int(bool(boxes)), ptr(dur), iptr(level), iptr(reach),
-                                              uptr(edges) if want_edges else None, iptr(iters)))
+        head = (self._h, n_scen, ptr(params), per_instance, int(speeds.size), ptr(speeds), _level_of(speeds, start, "start"), _level_of(speeds, end, "end"),
+                int(bool(common)), int(bool(boxes)))
+        outs = (ptr(dur), iptr(level), iptr(reach), uptr(edges) if want_edges else None, iptr(iters))
+        if reserve is None:
+            check(self._lib.upr_batch_retime_plan(*head, *outs))
+        else:
+            if frame not in ("world", "tray", 0, 1):
+                raise ValueError("frame must be 'world' or 'tray'")
+            dirs = None if dirs is None else cont(dirs).reshape(-1, 6)
+            check(self._lib.upr_batch_retime_plan_reserve(*head, 0 if dirs is None else dirs.shape[0], ptr(dirs), 1 if frame in ("tray", 1) else 0,
+                                                          float(reserve), *outs))
         return self._asked_for(dur, level, reach, edges, iters)
 
     def retimed_states(self, level, speeds):
