@@ -532,6 +532,31 @@ int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int pe
 int upr_batch_retime_plan_reserve(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds,
                                   int start_level, int end_level, int common, int boxes, int n_dir, const double* dirs, int frame,
                                   double reserve, double* duration, int* level, int* reach, unsigned* edges, int* iters);
+/* Replay of a time law on a clock (upright_amd/csrc/upr_replay.h): the states (q, qdot, qddot) of a retimed plan at t_k = t0 + k tick,
+ * k = 0 .. n_samp - 1, and the balance of the objects at every one of them -- between the knots, where the retiming above claims
+ * nothing.  speeds[n_lvl] as upr_batch_retime_plan's; level[B][N+1] ONE law per instance: lattice indices, or -1 throughout (no law);
+ * a law must not hold speed 0 over a segment.  Knot times T_0 = 0, T_{i+1} = T_i + 2 dt / (s_i + s_{i+1}), summed in this order; the
+ * duration is T_N.  A sample lies on the segment i with T_i <= t_k < T_{i+1} (on a knot: the departing side), at the path time tau of the
+ * law's constant sddot; the path between two knots is, per joint, the quintic Hermite interpolant of their records (q, v, a), C2 across
+ * the knots and equal to the plan's own cubic wherever the plan satisfies its dynamics; the state is (Q, s Q', s^2 Q'' + d Q').  Sample
+ * k EXISTS iff t_k <= T_N.
+ *       duration[B]              T_N, +inf without a law;
+ *       count[B]                 the existing samples (the first count ones), 0 without a law;
+ *       x[B][n_samp][3 nq]       the sample states; past the end the state at T_N, without a law (q_0, 0, 0);
+ *       rho, excess[B][n_samp][n_scen]  the distance of the cold projection and excess = rho / max(|b|, 1): accepted iff excess <= 1e-8,
+ *                                the rule of the friction margin; NaN for a sample that does not exist;
+ *       iters[B][n_samp][n_scen] least-squares solves, 0 for a sample that does not exist;
+ *       worst[B][n_scen]         the largest excess over the existing samples, NaN without any;
+ *       verdict[B][n_scen][3]    (first sample attaining worst or -1, first rejected sample or -1, number rejected);
+ *       box_first[B]             with boxes != 0 the first existing sample whose s Q' or s^2 Q'' + d Q' leaves the velocity or acceleration
+ *                                box of some joint, else -1.  Positions do not move, jerk is not judged.
+ *   params as upr_batch_speed_margin_plan (per_instance: a set per instance for all its samples).  tick must be finite and > 0, t0 finite
+ *   and >= 0, 1 <= n_samp <= 65536.  Every output may be NULL and is then not copied; x, rho, excess and worst must not all be NULL; with
+ *   x alone nothing is projected.  One level at speed 1 asks whether the plan as it stands is balanced between its knots.  Scratch,
+ *   timing and the state of the handle as the friction margin above. */
+int upr_batch_replay_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, const int* level,
+                          double tick, double t0, int n_samp, int boxes, double* duration, int* count, double* x, double* rho, double* excess,
+                          int* iters, double* worst, int* verdict, int* box_first);
 /* ------------------------------------------------------------------------------------------------
  * Disturbance margin (upright_amd/csrc/upr_disturb.h): how much tray acceleration the plan did not choose a state absorbs along given
  * directions with the objects still balanced.  dirs[n_dir][6] holds rows u = (u_alpha, u_a), rad/s^2 and m/s^2 per unit r, 1 <= n_dir
@@ -559,7 +584,7 @@ int upr_batch_disturbance_margin_plan(upr_batch* h, int n_scen, const double* pa
                                       int n_dir, const double* dirs, int frame, double r_max,
                                       double* reach, int* iters, double* window, int* knot, double* radius, int* binding);
 /* device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin, retiming
- * (with or without a reserve) or disturbance margin on the handle, HIP events around them (copies excluded) */
+ * (with or without a reserve), replay or disturbance margin on the handle, HIP events around them (copies excluded) */
 double upr_batch_balance_ms(upr_batch* h);
 
 /* raw device pointers for zero-copy consumers (torch / RCCL all-gather of solved trajectories):

@@ -1,7 +1,7 @@
 // upr_api_balance.hip -- the balance family of libupright_mi.so (include/upright_mi.h): request, validation, launcher and the
-// eighteen entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan* with upr_batch_balance_ms.  The one unit that includes
-// upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h and upr_retime_rsv.h: their kernels are defined here
-// and nowhere else.
+// nineteen entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan* / upr_batch_replay_plan with upr_batch_balance_ms.  The one
+// unit that includes upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h, upr_retime_rsv.h and
+// upr_replay.h: their kernels are defined here and nowhere else.
 // What crosses to upr_api.hip (upr_handle.h): upr_bal_resolve, the part of upr_batch_create that fills the handle's choice of form;
 // from there it takes upr_fail.  The family reads and writes the handle's bal, bal_buf / bal_cap, bal_ev and bal_ms, nothing else.
 #include "upr_handle.h"
@@ -15,6 +15,7 @@
 #include "upr_retime.h"
 #include "upr_disturb.h"
 #include "upr_retime_rsv.h"
+#include "upr_replay.h"
 
 // the form of a handle's balance family (UPR_BAL_FORM=0: the wave form for the one-body shapes too; tests)
 void upr_bal_resolve(upr_batch* h) {
@@ -27,7 +28,7 @@ void upr_bal_resolve(upr_batch* h) {
 
 namespace {
 
-// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h, upr_retime_rsv.h): the eighteen entry points end here, in balance_call.  An entry fills a REQUEST, which
+// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h, upr_retime_rsv.h, upr_replay.h): the nineteen entry points end here, in balance_call.  An entry fills a REQUEST, which
 // names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
 // go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
 // the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
@@ -38,8 +39,8 @@ namespace {
 enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
 // the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h) | the
 // path-acceleration margin (upr_pathacc.h) | the retiming of a plan on a speed lattice (upr_retime.h) | the disturbance margin
-// (upr_disturb.h) | the retiming with a reserve (upr_retime_rsv.h)
-enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5, BAL_DISTURB = 6, BAL_RETIME_RSV = 7 };
+// (upr_disturb.h) | the retiming with a reserve (upr_retime_rsv.h) | the replay of a time law on a clock (upr_replay.h)
+enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5, BAL_DISTURB = 6, BAL_RETIME_RSV = 7, BAL_REPLAY = 8 };
 struct bal_request {
     const char* who = "";     // the entry, as its messages name it
     const char* needs = "";   // ... and what they say about its required pointers
@@ -72,12 +73,20 @@ struct bal_request {
     // the retiming with a reserve: the retiming's fields, dirs / n_dir / frame as the disturbance margin's and the reserve r >= 0 every
     // end state must absorb along every +-u; the outputs and their layouts are the retiming's
     double reserve = 0.0;
+    // the replay (plan only): speeds / n_lvl and boxes as the retiming's; level_in [B][N + 1] one law per instance (lattice indices, or -1
+    // throughout: no law); the clock tick, t0, n_samp.  The points are the B n_samp samples.  out is rho [B][K][n_scen], limit the duration
+    // [B]; count [B], excess and iters [B][K][n_scen], worst [B][n_scen], verdict [B][n_scen][3], box_first [B], x_out [B][K][3 nq]
+    const int* level_in = nullptr; double tick = 0.0, t0 = 0.0; int n_samp = 0;
+    int *count = nullptr, *verdict = nullptr, *box_first = nullptr; double *excess = nullptr, *x_out = nullptr;
     // the answers on the host; all but the required ones may be NULL.  worst / worst_knot ([B][n_scen][n_grp]; plan, per group): the
     // largest kappa_hi over the knots of an instance, reduced on the device; out may then be NULL and kappa_hi stays on the device
     double* out = nullptr;   // rho | kappa_hi
     double *kappa_lo = nullptr, *z = nullptr, *y = nullptr; int* iters = nullptr; double* worst = nullptr; int* worst_knot = nullptr;
 };
-long long bal_points(const upr_batch* h, const bal_request& r) { return r.plan ? (long long)h->B * (h->d.N + 1) : r.n; }
+long long bal_points(const upr_batch* h, const bal_request& r) {
+    if (r.quantity == BAL_REPLAY) return (long long)h->B * r.n_samp;
+    return r.plan ? (long long)h->B * (h->d.N + 1) : r.n;
+}
 size_t bal_param_sets(const upr_batch* h, const bal_request& r) { return (size_t)(r.per ? (r.plan ? h->B : r.n) : 1) * r.n_scen; }
 
 size_t bal_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
@@ -117,7 +126,7 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
         return upr_fail("path-acceleration margin: d_max must be finite and > 0, speed finite and >= 0");
     if (r.quantity == BAL_MARGIN_GROUPS && balance_check_groups(h, r.n_grp, r.group_mask)) return 1;
     if (!r.plan && r.n <= 0) return 2;
-    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst && !r.level && !r.radius)) return refuse(r.needs);
+    if ((!r.plan && (!r.x || !r.params)) || (r.scale == BAL_MU_CONTACT && !r.mu_scale) || (!r.out && !r.worst && !r.level && !r.radius && !r.x_out && !r.excess)) return refuse(r.needs);
     if (r.plan && !r.params) {
         if (r.n_scen != 1) return refuse("params == NULL needs n_scen == 1 (every instance's own body parameters)");
     } else if (r.n_scen < 1) return refuse("n_scen must be >= 1");
@@ -127,12 +136,12 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
     if (balance_check_scales(r.mu_base, (size_t)r.n_scen * d.nc, "mu_base")) return 1;
     const long long n = bal_points(h, r);
     if (n > (1ll << 31) - 64 || n * r.n_scen * r.n_grp > (1ll << 36)) return upr_fail("balance check: too many points");
-    if (r.quantity == BAL_RETIME || r.quantity == BAL_RETIME_RSV) {
+    if (r.quantity == BAL_RETIME || r.quantity == BAL_RETIME_RSV || r.quantity == BAL_REPLAY) {
         bool ok = r.speeds && r.n_lvl >= 1 && r.n_lvl <= UPR_RET_MAX_LEVELS;
         for (int m = 0; ok && m < r.n_lvl; ++m) ok = std::isfinite(r.speeds[m]) && r.speeds[m] >= 0 && (m == 0 || r.speeds[m] > r.speeds[m - 1]);
         if (!ok) return upr_fail("retime: speeds must be 1 .. 32 finite values >= 0 in strictly increasing order");
         if (r.start < -1 || r.start >= r.n_lvl || r.end < -1 || r.end >= r.n_lvl) return upr_fail("retime: start and end must be -1 or a level index");
-        if (n * r.n_scen * r.n_lvl > (1ll << 36)) return upr_fail("balance check: too many points");   // (the jobs: a mask row each)
+        if (r.quantity != BAL_REPLAY && n * r.n_scen * r.n_lvl > (1ll << 36)) return upr_fail("balance check: too many points");   // (the jobs: a mask row each)
     }
     if (r.quantity == BAL_DISTURB) {
         if (!(r.r_max > 0) || !std::isfinite(r.r_max)) return upr_fail("disturbance margin: r_max must be finite and > 0");
@@ -157,23 +166,39 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
         if (!ok) return upr_fail("retime: dirs must be 1 .. 32 finite non-zero directions");
         if (r.frame != 0 && r.frame != 1) return upr_fail("retime: frame must be 0 (world) or 1 (tray)");
     }
+    if (r.quantity == BAL_REPLAY) {
+        if (!(r.tick > 0) || !std::isfinite(r.tick) || !(r.t0 >= 0) || !std::isfinite(r.t0)) return upr_fail("replay: tick must be finite and > 0, t0 finite and >= 0");
+        if (r.n_samp < 1 || r.n_samp > 65536) return upr_fail("replay: n_samp must be 1 .. 65536");
+        if (!r.level_in) return upr_fail("replay: level must not be NULL");
+        const int nk = d.N + 1;
+        for (int b = 0; b < h->B; ++b) {
+            const int* lv = r.level_in + (size_t)b * nk;
+            for (int i = 0; i < nk; ++i)
+                if (lv[i] < -1 || lv[i] >= r.n_lvl || ((lv[i] < 0) != (lv[0] < 0))) return upr_fail("replay: level must hold lattice indices, or -1 throughout a plan");
+        }
+        for (int b = 0; b < h->B; ++b) {
+            const int* lv = r.level_in + (size_t)b * nk;
+            for (int i = 0; lv[0] >= 0 && i + 1 < nk; ++i)
+                if (!(r.speeds[lv[i]] + r.speeds[lv[i + 1]] > 0.0)) return upr_fail("replay: a law must not hold speed 0 over a segment");
+        }
+    }
     return 0;
 }
 
 // form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
-// group, the speed margin, the path-acceleration margin, the edge masks of the retiming, the disturbance margin, the edge masks of the retiming with a reserve.  Every kernel takes
+// group, the speed margin, the path-acceleration margin, the edge masks of the retiming, the disturbance margin, the edge masks of the retiming with a reserve, the jobs of the replay.  Every kernel takes
 // (its record, upr_bal_dims, long long jobs); the record is upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the
 // groups, upr_spd_args for the speed margin, upr_pac_args for the path-acceleration margin, upr_ret_args for the retiming,
-// upr_dst_args for the disturbance margin and upr_ret_rsv_args for the retiming with a reserve.
-const void* const bal_kernels[2][10] = {
+// upr_dst_args for the disturbance margin, upr_ret_rsv_args for the retiming with a reserve and upr_rpl_args for the replay.
+const void* const bal_kernels[2][11] = {
     /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
                     (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel,
                     (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel, (const void*)upr_bal_disturb1_kernel,
-                    (const void*)upr_bal_retime_rsv1_kernel},
+                    (const void*)upr_bal_retime_rsv1_kernel, (const void*)upr_bal_replay1_kernel},
     /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
                     (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel,
                     (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel, (const void*)upr_bal_disturb_kernel,
-                    (const void*)upr_bal_retime_rsv_kernel}};
+                    (const void*)upr_bal_retime_rsv_kernel, (const void*)upr_bal_replay_kernel}};
 struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
 
 int balance_launch(upr_batch* h, const bal_request& r) {
@@ -182,12 +207,14 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, disturb = r.quantity == BAL_DISTURB;
     const bool speed = r.quantity == BAL_SPEED || pathacc || disturb;   // (speed: the four-double layout)
     const bool reserve = r.quantity == BAL_RETIME_RSV, retime = r.quantity == BAL_RETIME || reserve;   // (retime: what both retimings do)
-    const bool margin = r.quantity != BAL_RHO && !speed && !retime, groups = r.quantity == BAL_MARGIN_GROUPS;
+    // (replay: the sampler leaves the B K sample states where a points call uploads its x; jobs: somebody asks for more than the states)
+    const bool replay = r.quantity == BAL_REPLAY, jobs = !replay || r.out || r.excess || r.iters || r.worst || r.verdict;
+    const bool margin = r.quantity != BAL_RHO && !speed && !retime && !replay, groups = r.quantity == BAL_MARGIN_GROUPS;
     // (the retiming: a job is a mask row, (instance, scenario, segment, level); nplans outputs of the path kernel)
     const long long n = bal_points(h, r), njobs = retime ? (long long)h->B * r.n_scen * d.N * r.n_lvl : n * r.n_scen, ng = disturb ? r.n_dir : r.n_grp, nout = njobs * ng;
     const long long nplans = retime ? (long long)h->B * (r.common ? 1 : r.n_scen) : 0;
     // (the disturbance margin: njobs the jobs of one direction, ng the directions -- the groups' place, but the leading axis)
-    const bool want_worst = r.worst || r.worst_knot || r.radius || r.binding;
+    const bool want_worst = r.worst || r.worst_knot || r.radius || r.binding || r.verdict;
     const long long nworst = want_worst ? (long long)h->B * r.n_scen * (disturb ? 2 * ng : speed ? 2 : ng) : 0;
     const size_t per_out = speed ? 4 : 1, ends = speed ? 2 : 1;   // doubles of `out` and certificates per job
     const double* scale_host = groups ? r.mu_base : r.mu_scale;
@@ -206,16 +233,16 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const size_t o_z = region(sizeof(double) * nout * ends * L.ncol, r.z != nullptr, nullptr, r.z);
     const size_t o_it = region(sizeof(int) * nout, r.iters != nullptr, nullptr, r.iters);
     const size_t o_par = region(sizeof(double) * bal_param_sets(h, r) * d.nb * 10, r.params != nullptr, r.params, nullptr);
-    const size_t o_x = region(sizeof(double) * n * d.nx, !r.plan, r.x, nullptr);
+    const size_t o_x = region(sizeof(double) * n * (replay ? 3 * h->P.nq : d.nx), !r.plan || replay, replay ? nullptr : r.x, replay ? r.x_out : nullptr);
     const size_t o_mu = region(sizeof(double) * scale_count, scale_host != nullptr, scale_host, nullptr);
     const size_t o_lo = region(sizeof(double) * nout, r.kappa_lo != nullptr, nullptr, r.kappa_lo);
     const size_t o_y = region(sizeof(double) * nout * ends * L.m, r.y != nullptr, nullptr, r.y);
     const size_t o_gm = region(sizeof(unsigned) * ng, groups, r.group_mask, nullptr);
     const size_t o_w = region(sizeof(double) * nworst, want_worst, nullptr, r.worst);
-    const size_t o_wk = region(sizeof(int) * nworst, want_worst, nullptr, r.worst_knot);
-    const size_t o_lim = region(sizeof(double) * h->B * (pathacc ? 2 : 1), r.limit != nullptr, nullptr, r.limit);
+    const size_t o_wk = region(sizeof(int) * nworst, want_worst && !replay, nullptr, r.worst_knot);
+    const size_t o_lim = region(sizeof(double) * h->B * (pathacc ? 2 : 1), r.limit != nullptr, nullptr, r.limit);   // (replay: the duration)
     const size_t o_vee = region(sizeof(double) * n * 3, pathacc || retime, nullptr, nullptr);
-    const size_t o_spd = region(sizeof(double) * r.n_lvl, retime, r.speeds, nullptr);
+    const size_t o_spd = region(sizeof(double) * r.n_lvl, retime || replay, r.speeds, nullptr);
     const size_t o_edg = region(sizeof(unsigned) * nout, retime, nullptr, r.edges);
     const size_t o_arg = region((size_t)nplans * d.N * r.n_lvl, retime, nullptr, nullptr);
     const size_t o_lvl = region(sizeof(int) * nplans * (d.N + 1), retime, nullptr, r.level);
@@ -223,15 +250,30 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const size_t o_dir = region(sizeof(double) * (reserve ? r.n_dir : ng) * 6, disturb || reserve, r.dirs, nullptr);
     const size_t o_rad = region(sizeof(double) * h->B * r.n_scen, disturb && r.radius, nullptr, r.radius);
     const size_t o_bnd = region(sizeof(int) * h->B * r.n_scen * 3, disturb && r.binding, nullptr, r.binding);
+    const size_t o_lin = region(sizeof(int) * h->B * (d.N + 1), replay, r.level_in, nullptr);
+    const size_t o_cnt = region(sizeof(int) * h->B, replay, nullptr, r.count);
+    const size_t o_exc = region(sizeof(double) * nout, replay && jobs, nullptr, r.excess);
+    const size_t o_ver = region(sizeof(int) * nworst * 3, replay && r.verdict, nullptr, r.verdict);
+    const size_t o_bxf = region(sizeof(int) * h->B, replay && r.box_first, nullptr, r.box_first);
     if (balance_scratch(h, total)) return 1;
     char* base = (char*)h->bal_buf;
     for (int i = 0; i < nup; ++i) UPR_HIP(hipMemcpyAsync(base + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, h->stream));
     if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
     UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
-    const double* dx = r.plan ? h->xs : (const double*)(base + o_x);
+    const double* dx = (r.plan && !replay) ? h->xs : (const double*)(base + o_x);
     double *dst = (double*)(base + o_st), *drho = (double*)(base + o_rho);
     const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
-    if ((pathacc || retime) && h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_vee_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
+    if (replay) {
+        upr_rpl_sample_args Y;
+        Y.P = h->dP; Y.xs = h->xs; Y.speeds = (const double*)(base + o_spd); Y.level = (const int*)(base + o_lin); Y.nk = d.N + 1; Y.nx = d.nx;
+        Y.K = r.n_samp; Y.boxes = r.boxes ? 1 : 0; Y.h = h->P.dt; Y.tick = r.tick; Y.t0 = r.t0; Y.x = (double*)(base + o_x);
+        Y.duration = r.limit ? (double*)(base + o_lim) : nullptr; Y.count = (int*)(base + o_cnt); Y.box_first = r.box_first ? (int*)(base + o_bxf) : nullptr;
+        hipLaunchKernelGGL(upr_bal_replay_sample_kernel, dim3((unsigned)(h->B < 16384 ? h->B : 16384)), dim3(64), sizeof(double) * 2 * (d.N + 1), h->stream, Y,
+                           (long long)h->B);
+        UPR_HIP(hipGetLastError());
+    }
+    if (!jobs) {}   // (the states alone: the sampler was all)
+    else if ((pathacc || retime) && h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_vee_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
     else if (pathacc || retime) hipLaunchKernelGGL(upr_bal_state_vee_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
     else if (h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
     else hipLaunchKernelGGL(upr_bal_state_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst);
@@ -239,7 +281,7 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     upr_bal_args A;
     A.P = h->dP; A.n = (int)n; A.n_scen = r.n_scen; A.st = dst; A.eq_scale = d.eq_scale;
     A.params = r.params ? (const double*)(base + o_par) : h->body_params;
-    A.pdiv = r.plan ? ((r.per || !r.params) ? d.N + 1 : 0) : (r.per ? 1 : 0);   // points that share a parameter set
+    A.pdiv = r.plan ? ((r.per || !r.params) ? (replay ? r.n_samp : d.N + 1) : 0) : (r.per ? 1 : 0);   // points that share a parameter set
     A.rho = drho; A.z = r.z ? (double*)(base + o_z) : nullptr; A.iters = r.iters ? (int*)(base + o_it) : nullptr;
     A.mu_scale = r.mu_scale ? (const double*)(base + o_mu) : nullptr;
     upr_mar_args M;
@@ -266,6 +308,8 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     }
     upr_ret_rsv_args V;
     if (reserve) { V.T = T; V.dirs = (const double*)(base + o_dir); V.n_dir = r.n_dir; V.frame = r.frame; V.reserve = r.reserve; }
+    upr_rpl_args Rp;
+    if (replay) { Rp.J = A; Rp.J.rho = r.out ? drho : nullptr; Rp.count = (const int*)(base + o_cnt); Rp.K = r.n_samp; Rp.excess = (double*)(base + o_exc); }
     upr_grp_args X;
     if (groups) { X.M = M; X.n_grp = (int)ng; X.group_mask = (const unsigned*)(base + o_gm); X.mu_base = r.mu_base ? (const double*)(base + o_mu) : nullptr; }
     // lane form: 64 jobs per workgroup, the groups on the y axis.  Wave form: a workgroup is one wave and the jobs (for the groups:
@@ -273,9 +317,16 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     // the largest shape share a CU inside the 160 KiB)
     long long count = (wave && (groups || disturb)) ? nout : njobs;
     const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
-    void* args[] = {reserve ? (void*)&V : disturb ? (void*)&D : retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
-    UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
-    if (retime) {
+    void* args[] = {replay ? (void*)&Rp : reserve ? (void*)&V : disturb ? (void*)&D : retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
+    if (jobs) UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
+    if (replay) {
+        if (want_worst) {
+            hipLaunchKernelGGL(upr_bal_replay_plan_kernel, dim3((unsigned)((nworst + 63) / 64)), dim3(64), 0, h->stream, (const double*)(base + o_exc),
+                               (const int*)(base + o_cnt), r.n_samp, r.n_scen, nworst, r.worst ? (double*)(base + o_w) : nullptr,
+                               r.verdict ? (int*)(base + o_ver) : nullptr);
+            UPR_HIP(hipGetLastError());
+        }
+    } else if (retime) {
         upr_ret_path_args Q;
         Q.edges = T.edges; Q.speeds = T.speeds; Q.M = r.n_lvl; Q.nk = d.N + 1; Q.n_scen = r.n_scen; Q.common = r.common ? 1 : 0; Q.start = r.start; Q.end = r.end;
         Q.h = h->P.dt; Q.arg = (unsigned char*)(base + o_arg); Q.duration = drho; Q.level = (int*)(base + o_lvl); Q.reach = r.reach ? (int*)(base + o_rch) : nullptr;
@@ -454,6 +505,16 @@ int upr_batch_disturbance_margin_plan(upr_batch* h, int n_scen, const double* pa
                             .n_scen = n_scen, .params = params, .per = per_instance != 0, .quantity = BAL_DISTURB, .dirs = dirs, .n_dir = n_dir,
                             .frame = frame, .r_max = r_max, .radius = radius, .binding = binding, .out = reach, .iters = iters, .worst = window,
                             .worst_knot = knot});
+}
+
+int upr_batch_replay_plan(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, const int* level, double tick,
+                          double t0, int n_samp, int boxes, double* duration, int* count, double* x, double* rho, double* excess, int* iters, double* worst,
+                          int* verdict, int* box_first) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_replay_plan", .needs = "x, rho, excess and worst must not all be NULL", .plan = true, .n_scen = n_scen,
+                            .params = params, .per = per_instance != 0, .quantity = BAL_REPLAY, .limit = duration, .speeds = speeds, .n_lvl = n_lvl,
+                            .boxes = boxes != 0, .level_in = level, .tick = tick, .t0 = t0, .n_samp = n_samp, .count = count, .verdict = verdict,
+                            .box_first = box_first, .excess = excess, .x_out = x, .out = rho, .iters = iters, .worst = worst});
 }
 
 double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }

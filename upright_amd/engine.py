@@ -723,9 +723,72 @@ class BatchMPC:
             return np.concatenate([q + 0.0 * sk[..., None], sk[..., None] * v, (sk * sk)[..., None] * a + d[..., None] * v], axis=-1)
         return t, side(x[..., :-1, :], s0), side(x[..., 1:, :], s1)
 
+    def replay_plan(self, level, speeds, tick, params=None, t0=0.0, n_samples=None, boxes=True, want_rho=False, want_iters=False, reductions=False):
+        """(t, x, excess): the time law `level` of retime_plan replayed on a clock (upr_batch_replay_plan) -- the states a tracking
+        controller needs at t_k = t0 + k tick and the balance of the objects at every one of them, BETWEEN the knots too, where
+        retime_plan claims nothing.  level (B, N + 1) int: ONE law per instance, indices into speeds, or -1 throughout (no law); a (B,
+        n_scen, N + 1) array is refused: call once per scenario with level[:, sc].  speeds as in retime_plan; tick > 0, t0 >= 0;
+        n_samples None: floor((the largest finite duration - t0) / tick) + 1 (at least 1), the durations being retimed_states' t[.., N].
+        On segment i the law keeps sddot = d_i, so a sample t' after knot i has the speed s = s_i + d_i t' and lies at the path time tau
+        = t' (s_i + d_i t' / 2); the path between two knots is, per joint, the quintic Hermite interpolant Q of their records (q, v, a)
+        -- C2 across the knots, the plan's own cubic wherever the plan satisfies its dynamics, retimed_states' dep at t' = 0 and arr at
+        the end of the segment; a sample on a knot takes the departing side.  params as in balance_check_plan.
+
+        t (K,); x (B, K, 3 nq) = (Q, s Q', s^2 Q'' + d Q'); excess (B, K, n_scen) = rho / max(|b|, 1) of the balance check at x: the sample
+        is accepted iff excess <= 1e-8, the rule of retime_plan.  Sample k exists iff t_k <= the duration of its plan; x and excess are
+        NaN past the end and for a plan without a law.  With want_rho / want_iters the tuple (t, x, excess, rho, iters) restricted to
+        what was asked for.  reductions=True: (duration (B,), count (B,), worst (B, n_scen), verdict (B, n_scen, 3), box_first (B,))
+        alone, reduced on the device, nothing else is downloaded -- count the existing samples, worst the largest excess over them (NaN
+        without any), verdict = (first sample attaining worst, first rejected sample or -1, number rejected), box_first (boxes=True) the
+        first existing sample at which some joint's velocity or acceleration leaves its bounds, else -1.  Jerk is not judged.
+
+        One level at speed 1 asks whether the plan as it stands is balanced between its knots.  A law accepted at every knot can leave
+        the cone inside a segment: a translation whose path acceleration peaks at 0.8 mu g BETWEEN two knots (tests/retime_ref.py,
+        slide_case), replayed uniformly at 1.1185 -- 1.1185^2 * 0.8 = 1.0008 > 1 while every knot keeps a margin of 1.5e-3 mu g:
+
+            duration, level = mpc.retime_plan([1.1185], boxes=False)                      # finite: every knot is balanced
+            t, x, excess = mpc.replay_plan(level[:, 0], [1.1185], 0.01, boxes=False)       # 179 samples at 100 Hz
+            np.flatnonzero(excess[0, :, 0] > 1e-8)                                         # 37 38 39 140 141 142: between knots 4-5 and 15-16
+        """
+        speeds = cont(speeds).reshape(-1)
+        level = np.asarray(level)
+        if level.ndim == 3:
+            raise ValueError("replay_plan takes one law per instance, level (B, N + 1): call once per scenario with level[:, sc]")
+        if level.shape != (self.B, self.N + 1):
+            raise ValueError("level must have the shape (B, N + 1)")
+        level = cont(level, dtype=np.int32)
+        n_scen, per_instance, params = self._plan_params(params)
+        if n_samples is None:
+            ok = (level >= 0).all(axis=-1) & (level < speeds.size).all(axis=-1)
+            s = speeds[np.clip(level, 0, speeds.size - 1)]
+            with np.errstate(divide="ignore"):
+                dur = np.cumsum(2.0 * float(self.problem.dt) / (s[:, :-1] + s[:, 1:]), axis=-1)[:, -1]
+            dur = dur[ok & np.isfinite(dur)]
+            n_samples = max(1, int(np.floor((dur.max() - t0) / tick)) + 1) if dur.size and tick > 0 and dur.max() >= t0 else 1
+        K = int(n_samples)
+        if K < 1:
+            raise ValueError("n_samples must be >= 1")   # (the sizes of the outputs; every other refusal is the library's)
+        head = (self._h, n_scen, ptr(params), per_instance, int(speeds.size), ptr(speeds), iptr(level), float(tick), float(t0), K, int(bool(boxes)))
+        if reductions:
+            if want_rho or want_iters:
+                raise ValueError("reductions=True returns the reductions alone")
+            dur, count, bfirst = self._outputs((self.B,), (True, (), F8), (True, (), I4), (True, (), I4))
+            worst, verdict = self._outputs((self.B, n_scen), (True, (), F8), (True, (3,), I4))
+            check(self._lib.upr_batch_replay_plan(*head, ptr(dur), iptr(count), None, None, None, None, ptr(worst), iptr(verdict), iptr(bfirst)))
+            return dur, count, worst, verdict, bfirst
+        count, = self._outputs((self.B,), (True, (), I4))
+        x, = self._outputs((self.B, K), (True, (3 * self.problem.nq,), F8))
+        excess, rho, iters = self._outputs((self.B, K, n_scen), (True, (), F8), (want_rho, (), F8), (want_iters, (), I4))
+        check(self._lib.upr_batch_replay_plan(*head, None, iptr(count), ptr(x), ptr(rho), ptr(excess), iptr(iters), None, None, None))
+        gone = np.arange(K)[None, :] >= count[:, None]
+        x[gone] = np.nan
+        excess[gone] = np.nan
+        t = float(t0) + np.arange(K, dtype=np.float64) * float(tick)
+        return self._asked_for(t, x, excess, rho, iters)
+
     def balance_ms(self):
-        """Device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin, retiming
-        or disturbance margin (HIP events around them)."""
+        """Device time (ms) of the kernel launches of the last balance check, friction margin, speed margin, path-acceleration margin, retiming,
+        replay or disturbance margin (HIP events around them)."""
         return float(self._lib.upr_batch_balance_ms(self._h))
 
     def balance_forces(self, z):
