@@ -532,6 +532,22 @@ int upr_batch_retime_plan(upr_batch* h, int n_scen, const double* params, int pe
 int upr_batch_retime_plan_reserve(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds,
                                   int start_level, int end_level, int common, int boxes, int n_dir, const double* dirs, int frame,
                                   double reserve, double* duration, int* level, int* reach, unsigned* edges, int* iters);
+/* Retiming with substeps (upright_amd/csrc/upr_retime_sub.h): the fastest time law on the lattice whose every segment is balanced at
+ * substeps - 1 interior points of the path as well as at its two knots.  Lattice, edges, d, boxes, common, start / end, the programme,
+ * the outputs, their layouts and the required-pointer refusal are upr_batch_retime_plan's; substeps = R must be 1 .. 16.  Segment i gets
+ * the path points tau_r = r dt / R, r = 0 .. R: r = 0 and r = R are the knots i and i + 1, their records the plan's own; for 0 < r < R
+ * the record is (Q, Q', Q'') of the quintic Hermite interpolant of upr_batch_replay_plan below at tau_r.  On the edge m -> m' the speed at
+ * point r is s_r = sqrt(((R - r) s_m^2 + r s_m'^2) / R) (constant sddot makes s^2 linear in tau; s_0 = s_m, s_R = s_m' exactly), d is the
+ * edge's, the state (Q, s_r Q', s_r^2 Q'' + d Q').  The edge is admissible iff it exists, with boxes s_r Q' and s_r^2 Q'' + d Q' of every
+ * joint lie inside their boxes at every r, and all R + 1 states are accepted by the rule, unchanged.  Evaluated in a fixed order -- the
+ * boxes at r = 0, R, then 1 .. R - 1; the projections departing, arriving, then r = 1 .. R - 1, stopping at the first rejection -- so
+ * iters (at most n_lvl (R + 1) projections per mask row) is reproducible.  With substeps == 1 every output equals upr_batch_retime_plan's
+ * bit for bit.
+ *   Claimed: the law is balanced at the knots and at the R - 1 interior path points of every segment.  NOT claimed: anything between
+ *   those points -- upr_batch_replay_plan on the returned law is the caller's check -- and jerk. */
+int upr_batch_retime_plan_substeps(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds,
+                                   int start_level, int end_level, int common, int boxes, int substeps, double* duration, int* level,
+                                   int* reach, unsigned* edges, int* iters);
 /* Replay of a time law on a clock (upright_amd/csrc/upr_replay.h): the states (q, qdot, qddot) of a retimed plan at t_k = t0 + k tick,
  * k = 0 .. n_samp - 1, and the balance of the objects at every one of them -- between the knots, where the retiming above claims
  * nothing.  speeds[n_lvl] as upr_batch_retime_plan's; level[B][N+1] ONE law per instance: lattice indices, or -1 throughout (no law);

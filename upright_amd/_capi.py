@@ -173,6 +173,8 @@ PROTOTYPES = [
     ("upr_batch_retime_plan", C.c_int, [C.c_void_p, C.c_int, dp, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_int, C.c_int, dp, ip, ip, C.POINTER(C.c_uint), ip]),
     ("upr_batch_retime_plan_reserve", C.c_int, [C.c_void_p, C.c_int, dp, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_int,
                                                 C.c_double, dp, ip, ip, C.POINTER(C.c_uint), ip]),
+    ("upr_batch_retime_plan_substeps", C.c_int, [C.c_void_p, C.c_int, dp, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, ip, ip,
+                                                 C.POINTER(C.c_uint), ip]),
     ("upr_batch_replay_plan", C.c_int, [C.c_void_p, C.c_int, dp, C.c_int, C.c_int, dp, ip, C.c_double, C.c_double, C.c_int, C.c_int, dp, ip, dp, dp, dp, ip,
                                         dp, ip, ip]),
     ("upr_batch_disturbance_margin_points", C.c_int, [C.c_void_p, C.c_int, dp, C.c_int, dp, C.c_int, C.c_int, dp, C.c_int, C.c_double, dp, dp, dp, ip]),

@@ -1,7 +1,7 @@
 // upr_api_balance.hip -- the balance family of libupright_mi.so (include/upright_mi.h): request, validation, launcher and the
-// nineteen entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan* / upr_batch_replay_plan with upr_batch_balance_ms.  The one
-// unit that includes upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h, upr_retime_rsv.h and
-// upr_replay.h: their kernels are defined here and nowhere else.
+// twenty entries upr_batch_balance_* / *_margin_* / upr_batch_retime_plan* / upr_batch_replay_plan with upr_batch_balance_ms.  The one
+// unit that includes upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h, upr_retime_rsv.h,
+// upr_replay.h and upr_retime_sub.h: their kernels are defined here and nowhere else.
 // What crosses to upr_api.hip (upr_handle.h): upr_bal_resolve, the part of upr_batch_create that fills the handle's choice of form;
 // from there it takes upr_fail.  The family reads and writes the handle's bal, bal_buf / bal_cap, bal_ev and bal_ms, nothing else.
 #include "upr_handle.h"
@@ -16,6 +16,7 @@
 #include "upr_disturb.h"
 #include "upr_retime_rsv.h"
 #include "upr_replay.h"
+#include "upr_retime_sub.h"
 
 // the form of a handle's balance family (UPR_BAL_FORM=0: the wave form for the one-body shapes too; tests)
 void upr_bal_resolve(upr_batch* h) {
@@ -28,7 +29,7 @@ void upr_bal_resolve(upr_batch* h) {
 
 namespace {
 
-// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h, upr_retime_rsv.h, upr_replay.h): the nineteen entry points end here, in balance_call.  An entry fills a REQUEST, which
+// ---- balance family (upr_balance.h, upr_margin.h, upr_speed.h, upr_pathacc.h, upr_retime.h, upr_disturb.h, upr_retime_rsv.h, upr_replay.h, upr_retime_sub.h): the twenty entry points end here, in balance_call.  An entry fills a REQUEST, which
 // names what the call is: where its points and its scenarios come from, which friction scale, which quantity, where the answers
 // go.  balance_validate holds every refusal of the family, in one order.  What depends on the handle alone -- the layout of a job,
 // the LDS of the wave form, lane or wave -- is the CHOICE resolved at upr_batch_create (upr_bal_choice).  The LAUNCHER reads the two:
@@ -39,8 +40,10 @@ namespace {
 enum { BAL_MU_NONE = 0, BAL_MU_SCENARIO = 1, BAL_MU_CONTACT = 2 };   // the friction scale: ones | [n_scen] | [n_scen][nc]
 // the quantity: the distance rho | the common friction margin | one per contact group | the speed margin (upr_speed.h) | the
 // path-acceleration margin (upr_pathacc.h) | the retiming of a plan on a speed lattice (upr_retime.h) | the disturbance margin
-// (upr_disturb.h) | the retiming with a reserve (upr_retime_rsv.h) | the replay of a time law on a clock (upr_replay.h)
-enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5, BAL_DISTURB = 6, BAL_RETIME_RSV = 7, BAL_REPLAY = 8 };
+// (upr_disturb.h) | the retiming with a reserve (upr_retime_rsv.h) | the replay of a time law on a clock (upr_replay.h) | the retiming
+// with substeps (upr_retime_sub.h)
+enum { BAL_RHO = 0, BAL_MARGIN = 1, BAL_MARGIN_GROUPS = 2, BAL_SPEED = 3, BAL_PATHACC = 4, BAL_RETIME = 5, BAL_DISTURB = 6, BAL_RETIME_RSV = 7, BAL_REPLAY = 8,
+       BAL_RETIME_SUB = 9 };
 struct bal_request {
     const char* who = "";     // the entry, as its messages name it
     const char* needs = "";   // ... and what they say about its required pointers
@@ -73,6 +76,9 @@ struct bal_request {
     // the retiming with a reserve: the retiming's fields, dirs / n_dir / frame as the disturbance margin's and the reserve r >= 0 every
     // end state must absorb along every +-u; the outputs and their layouts are the retiming's
     double reserve = 0.0;
+    // the retiming with substeps: the retiming's fields and substeps = R, the path points per segment beyond its departing knot at which
+    // an edge must be balanced; the points are the B (N R + 1) points of the fine plan; the outputs and their layouts are the retiming's
+    int substeps = 1;
     // the replay (plan only): speeds / n_lvl and boxes as the retiming's; level_in [B][N + 1] one law per instance (lattice indices, or -1
     // throughout: no law); the clock tick, t0, n_samp.  The points are the B n_samp samples.  out is rho [B][K][n_scen], limit the duration
     // [B]; count [B], excess and iters [B][K][n_scen], worst [B][n_scen], verdict [B][n_scen][3], box_first [B], x_out [B][K][3 nq]
@@ -85,6 +91,8 @@ struct bal_request {
 };
 long long bal_points(const upr_batch* h, const bal_request& r) {
     if (r.quantity == BAL_REPLAY) return (long long)h->B * r.n_samp;
+    // (a substeps outside 1 .. UPR_SUB_MAX counts as 1 here: the checks on the points come first, the refusal of the value is its own)
+    if (r.quantity == BAL_RETIME_SUB) return (long long)h->B * ((long long)h->d.N * (r.substeps >= 1 && r.substeps <= UPR_SUB_MAX ? r.substeps : 1) + 1);
     return r.plan ? (long long)h->B * (h->d.N + 1) : r.n;
 }
 size_t bal_param_sets(const upr_batch* h, const bal_request& r) { return (size_t)(r.per ? (r.plan ? h->B : r.n) : 1) * r.n_scen; }
@@ -136,12 +144,15 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
     if (balance_check_scales(r.mu_base, (size_t)r.n_scen * d.nc, "mu_base")) return 1;
     const long long n = bal_points(h, r);
     if (n > (1ll << 31) - 64 || n * r.n_scen * r.n_grp > (1ll << 36)) return upr_fail("balance check: too many points");
-    if (r.quantity == BAL_RETIME || r.quantity == BAL_RETIME_RSV || r.quantity == BAL_REPLAY) {
+    if (r.quantity == BAL_RETIME || r.quantity == BAL_RETIME_RSV || r.quantity == BAL_REPLAY || r.quantity == BAL_RETIME_SUB) {
         bool ok = r.speeds && r.n_lvl >= 1 && r.n_lvl <= UPR_RET_MAX_LEVELS;
         for (int m = 0; ok && m < r.n_lvl; ++m) ok = std::isfinite(r.speeds[m]) && r.speeds[m] >= 0 && (m == 0 || r.speeds[m] > r.speeds[m - 1]);
         if (!ok) return upr_fail("retime: speeds must be 1 .. 32 finite values >= 0 in strictly increasing order");
         if (r.start < -1 || r.start >= r.n_lvl || r.end < -1 || r.end >= r.n_lvl) return upr_fail("retime: start and end must be -1 or a level index");
-        if (r.quantity != BAL_REPLAY && n * r.n_scen * r.n_lvl > (1ll << 36)) return upr_fail("balance check: too many points");   // (the jobs: a mask row each)
+        if (r.quantity == BAL_RETIME_SUB && (r.substeps < 1 || r.substeps > UPR_SUB_MAX)) return upr_fail("retime: substeps must be 1 .. 16");
+        // (the jobs: a mask row each, counted on the knots of the plan)
+        const long long knots = r.quantity == BAL_RETIME_SUB ? (long long)h->B * (d.N + 1) : n;
+        if (r.quantity != BAL_REPLAY && knots * r.n_scen * r.n_lvl > (1ll << 36)) return upr_fail("balance check: too many points");
     }
     if (r.quantity == BAL_DISTURB) {
         if (!(r.r_max > 0) || !std::isfinite(r.r_max)) return upr_fail("disturbance margin: r_max must be finite and > 0");
@@ -186,19 +197,20 @@ int balance_validate(const upr_batch* h, const bal_request& r) {
 }
 
 // form x quantity -> kernel; the columns: rho, rho with mu_scale, rho with a scale per contact, the common margin, the margin per
-// group, the speed margin, the path-acceleration margin, the edge masks of the retiming, the disturbance margin, the edge masks of the retiming with a reserve, the jobs of the replay.  Every kernel takes
+// group, the speed margin, the path-acceleration margin, the edge masks of the retiming, the disturbance margin, the edge masks of the retiming with a reserve, the jobs of the replay, the edge masks of the retiming with substeps.  Every kernel takes
 // (its record, upr_bal_dims, long long jobs); the record is upr_bal_args, upr_mar_args for the common margin, upr_grp_args for the
 // groups, upr_spd_args for the speed margin, upr_pac_args for the path-acceleration margin, upr_ret_args for the retiming,
-// upr_dst_args for the disturbance margin, upr_ret_rsv_args for the retiming with a reserve and upr_rpl_args for the replay.
-const void* const bal_kernels[2][11] = {
+// upr_dst_args for the disturbance margin, upr_ret_rsv_args for the retiming with a reserve, upr_rpl_args for the replay and
+// upr_ret_sub_args for the retiming with substeps.
+const void* const bal_kernels[2][12] = {
     /* BAL_LANE */ {(const void*)upr_bal_project1_kernel, (const void*)upr_bal_project1_mu_kernel, (const void*)upr_bal_project1_cmu_kernel,
                     (const void*)upr_bal_margin1_kernel, (const void*)upr_bal_margin1_grp_kernel, (const void*)upr_bal_speed1_kernel,
                     (const void*)upr_bal_pathacc1_kernel, (const void*)upr_bal_retime1_kernel, (const void*)upr_bal_disturb1_kernel,
-                    (const void*)upr_bal_retime_rsv1_kernel, (const void*)upr_bal_replay1_kernel},
+                    (const void*)upr_bal_retime_rsv1_kernel, (const void*)upr_bal_replay1_kernel, (const void*)upr_bal_retime_sub1_kernel},
     /* BAL_WAVE */ {(const void*)upr_bal_project_kernel, (const void*)upr_bal_project_mu_kernel, (const void*)upr_bal_project_cmu_kernel,
                     (const void*)upr_bal_margin_kernel, (const void*)upr_bal_margin_grp_kernel, (const void*)upr_bal_speed_kernel,
                     (const void*)upr_bal_pathacc_kernel, (const void*)upr_bal_retime_kernel, (const void*)upr_bal_disturb_kernel,
-                    (const void*)upr_bal_retime_rsv_kernel, (const void*)upr_bal_replay_kernel}};
+                    (const void*)upr_bal_retime_rsv_kernel, (const void*)upr_bal_replay_kernel, (const void*)upr_bal_retime_sub_kernel}};
 struct bal_copy { size_t off; void* host; size_t bytes; };   // a region of the scratch block and its side on the host
 
 int balance_launch(upr_batch* h, const bal_request& r) {
@@ -206,7 +218,8 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     upr_bal_dims L = h->bal.L;
     const bool wave = h->bal.form == BAL_WAVE, pathacc = r.quantity == BAL_PATHACC, disturb = r.quantity == BAL_DISTURB;
     const bool speed = r.quantity == BAL_SPEED || pathacc || disturb;   // (speed: the four-double layout)
-    const bool reserve = r.quantity == BAL_RETIME_RSV, retime = r.quantity == BAL_RETIME || reserve;   // (retime: what both retimings do)
+    const bool reserve = r.quantity == BAL_RETIME_RSV, sub = r.quantity == BAL_RETIME_SUB;
+    const bool retime = r.quantity == BAL_RETIME || reserve || sub;   // (retime: what the three retimings do)
     // (replay: the sampler leaves the B K sample states where a points call uploads its x; jobs: somebody asks for more than the states)
     const bool replay = r.quantity == BAL_REPLAY, jobs = !replay || r.out || r.excess || r.iters || r.worst || r.verdict;
     const bool margin = r.quantity != BAL_RHO && !speed && !retime && !replay, groups = r.quantity == BAL_MARGIN_GROUPS;
@@ -255,12 +268,13 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     const size_t o_exc = region(sizeof(double) * nout, replay && jobs, nullptr, r.excess);
     const size_t o_ver = region(sizeof(int) * nworst * 3, replay && r.verdict, nullptr, r.verdict);
     const size_t o_bxf = region(sizeof(int) * h->B, replay && r.box_first, nullptr, r.box_first);
+    const size_t o_xf = region(sizeof(double) * n * 3 * h->P.nq, sub, nullptr, nullptr);   // (the fine plan)
     if (balance_scratch(h, total)) return 1;
     char* base = (char*)h->bal_buf;
     for (int i = 0; i < nup; ++i) UPR_HIP(hipMemcpyAsync(base + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, h->stream));
     if (!h->bal_ev[0]) { UPR_HIP(hipEventCreate(&h->bal_ev[0])); UPR_HIP(hipEventCreate(&h->bal_ev[1])); }
     UPR_HIP(hipEventRecord(h->bal_ev[0], h->stream));
-    const double* dx = (r.plan && !replay) ? h->xs : (const double*)(base + o_x);
+    const double* dx = sub ? (const double*)(base + o_xf) : (r.plan && !replay) ? h->xs : (const double*)(base + o_x);
     double *dst = (double*)(base + o_st), *drho = (double*)(base + o_rho);
     const dim3 sg((unsigned)((n + 63) / 64)), sb(64);
     if (replay) {
@@ -272,6 +286,12 @@ int balance_launch(upr_batch* h, const bal_request& r) {
                            (long long)h->B);
         UPR_HIP(hipGetLastError());
     }
+    if (sub) {
+        upr_sub_refine_args F;
+        F.P = h->dP; F.xs = h->xs; F.nk = d.N + 1; F.nx = d.nx; F.R = r.substeps; F.h = h->P.dt; F.xf = (double*)(base + o_xf);
+        hipLaunchKernelGGL(upr_bal_refine_kernel, dim3((unsigned)((n + 63) / 64 < 16384 ? (n + 63) / 64 : 16384)), dim3(64), 0, h->stream, F, n);
+        UPR_HIP(hipGetLastError());
+    }
     if (!jobs) {}   // (the states alone: the sampler was all)
     else if ((pathacc || retime) && h->P.nq == 6) hipLaunchKernelGGL(upr_bal_state_vee_kernel<6>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
     else if (pathacc || retime) hipLaunchKernelGGL(upr_bal_state_vee_kernel<9>, sg, sb, 0, h->stream, h->dP, (int)n, dx, dst, (double*)(base + o_vee));
@@ -281,7 +301,7 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     upr_bal_args A;
     A.P = h->dP; A.n = (int)n; A.n_scen = r.n_scen; A.st = dst; A.eq_scale = d.eq_scale;
     A.params = r.params ? (const double*)(base + o_par) : h->body_params;
-    A.pdiv = r.plan ? ((r.per || !r.params) ? (replay ? r.n_samp : d.N + 1) : 0) : (r.per ? 1 : 0);   // points that share a parameter set
+    A.pdiv = r.plan ? ((r.per || !r.params) ? (replay ? r.n_samp : sub ? d.N * r.substeps + 1 : d.N + 1) : 0) : (r.per ? 1 : 0);   // points that share a parameter set
     A.rho = drho; A.z = r.z ? (double*)(base + o_z) : nullptr; A.iters = r.iters ? (int*)(base + o_it) : nullptr;
     A.mu_scale = r.mu_scale ? (const double*)(base + o_mu) : nullptr;
     upr_mar_args M;
@@ -304,10 +324,12 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     upr_ret_args T;
     if (retime) {
         T.J = A; T.J.rho = nullptr; T.vee = (const double*)(base + o_vee); T.xs = dx; T.speeds = (const double*)(base + o_spd); T.M = r.n_lvl;
-        T.nk = d.N + 1; T.nx = d.nx; T.boxes = r.boxes ? 1 : 0; T.h = h->P.dt; T.edges = (unsigned*)(base + o_edg);
+        T.nk = d.N + 1; T.nx = sub ? 3 * h->P.nq : d.nx; T.boxes = r.boxes ? 1 : 0; T.h = h->P.dt; T.edges = (unsigned*)(base + o_edg);
     }
     upr_ret_rsv_args V;
     if (reserve) { V.T = T; V.dirs = (const double*)(base + o_dir); V.n_dir = r.n_dir; V.frame = r.frame; V.reserve = r.reserve; }
+    upr_ret_sub_args U;
+    if (sub) { U.T = T; U.R = r.substeps; }
     upr_rpl_args Rp;
     if (replay) { Rp.J = A; Rp.J.rho = r.out ? drho : nullptr; Rp.count = (const int*)(base + o_cnt); Rp.K = r.n_samp; Rp.excess = (double*)(base + o_exc); }
     upr_grp_args X;
@@ -317,7 +339,7 @@ int balance_launch(upr_batch* h, const bal_request& r) {
     // the largest shape share a CU inside the 160 KiB)
     long long count = (wave && (groups || disturb)) ? nout : njobs;
     const dim3 grid = wave ? dim3((unsigned)(count < 16384 ? count : 16384)) : dim3((unsigned)((njobs + 63) / 64), (unsigned)ng);
-    void* args[] = {replay ? (void*)&Rp : reserve ? (void*)&V : disturb ? (void*)&D : retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
+    void* args[] = {replay ? (void*)&Rp : sub ? (void*)&U : reserve ? (void*)&V : disturb ? (void*)&D : retime ? (void*)&T : pathacc ? (void*)&C : speed ? (void*)&S : groups ? (void*)&X : margin ? (void*)&M : (void*)&A, &L, &count};
     if (jobs) UPR_HIP(hipLaunchKernel(bal_kernels[h->bal.form][r.quantity != BAL_RHO ? 2 + r.quantity : r.scale], grid, dim3(64), args, wave ? h->bal.lds : 0, h->stream));
     if (replay) {
         if (want_worst) {
@@ -515,6 +537,15 @@ int upr_batch_replay_plan(upr_batch* h, int n_scen, const double* params, int pe
                             .params = params, .per = per_instance != 0, .quantity = BAL_REPLAY, .limit = duration, .speeds = speeds, .n_lvl = n_lvl,
                             .boxes = boxes != 0, .level_in = level, .tick = tick, .t0 = t0, .n_samp = n_samp, .count = count, .verdict = verdict,
                             .box_first = box_first, .excess = excess, .x_out = x, .out = rho, .iters = iters, .worst = worst});
+}
+
+int upr_batch_retime_plan_substeps(upr_batch* h, int n_scen, const double* params, int per_instance, int n_lvl, const double* speeds, int start_level,
+                                   int end_level, int common, int boxes, int substeps, double* duration, int* level, int* reach, unsigned* edges, int* iters) {
+    UPR_ENTER(h);
+    return balance_call(h, {.who = "upr_batch_retime_plan_substeps", .needs = "duration and level must not both be NULL", .plan = true, .n_scen = n_scen,
+                            .params = params, .per = per_instance != 0, .quantity = BAL_RETIME_SUB, .speeds = speeds, .n_lvl = n_lvl, .start = start_level,
+                            .end = end_level, .common = common != 0, .boxes = boxes != 0, .level = level, .reach = reach, .edges = edges, .substeps = substeps,
+                            .out = duration, .iters = iters});
 }
 
 double upr_batch_balance_ms(upr_batch* h) { return h ? h->bal_ms : 0.0; }

@@ -634,7 +634,7 @@ class BatchMPC:
         return self._asked_for(reach[..., 0::2].copy(), reach[..., 1::2].copy() if want_out else None, iters)
 
     def retime_plan(self, speeds, params=None, start=None, end=None, common=False, boxes=True, want_reach=False, want_edges=False, want_iters=False,
-                    reserve=None, dirs=None, frame="tray"):
+                    reserve=None, dirs=None, frame="tray", substeps=1):
         """(duration, level): the fastest time law on the lattice `speeds` that replays the geometric path of the current plan with the
         objects balanced at every knot (upr_batch_retime_plan), where speed_margin_plan could only offer one uniform factor.  speeds
         (M,): replay speeds s_0 < s_1 < .., finite, >= 0, 1 <= M <= 32.  The law gives knot i the speed speeds[level[i]] and keeps
@@ -679,8 +679,27 @@ class BatchMPC:
 
             zx = np.array([[0, 0, 0, 0, 0, 1.0], [0, 0, 0, 1.0, 0, 0]])       # the tray's own z and x axes
             duration, level = mpc.retime_plan(speeds, reserve=0.5, dirs=zx)   # every knot absorbs 0.5 m/s^2 along +-z and +-x
+
+        substeps=R (an integer 1 .. 16; upr_batch_retime_plan_substeps): everything above holds at the knots only.  With R > 1 an edge is
+        admissible only if the objects are also balanced at the R - 1 interior path points tau_r = r dt / R of its segment: the point
+        (Q, Q', Q'') of replay_plan's quintic Hermite path there, at the speed s_r = sqrt(((R - r) s_i^2 + r s_{i+1}^2) / R) the edge's
+        constant sddot gives it, the state (Q, s_r Q', s_r^2 Q'' + d_i Q'); with boxes the interior states stay inside the bounds too.  The
+        law is still one level per knot: replay_plan and retimed_states take it as it is, retimed_substates(level, speeds, R) gives the
+        states that were judged.  iters at most M (R + 1) projections per row.  Nothing is claimed between the substep points:
+        replay_plan on the returned law is the check.  substeps=1 (the default) is the plain call; substeps > 1 together with reserve is
+        a ValueError.  The slide of replay_plan's example, which the plain call accepts at 1.1185 and a 10 ms clock rejects on six
+        samples:
+
+            mpc.retime_plan([1.1185], boxes=False, substeps=2)[0]                          # 1.788109: the midpoints miss the peak
+            mpc.retime_plan([1.1185], boxes=False, substeps=4)[0]                          # inf: the points 1/4 of segment 4, 3/4 of segment 15
+            duration, level = mpc.retime_plan([1.11, 1.1185], boxes=False, substeps=4)     # 1.789473, level 0 at knots 5 and 15 only
+            mpc.replay_plan(level[:, 0], [1.11, 1.1185], 0.01, boxes=False, reductions=True)[3][..., 2]   # 0 samples rejected
         """
         speeds = cont(speeds).reshape(-1)
+        if int(substeps) != substeps:
+            raise ValueError("substeps must be an integer")
+        if substeps != 1 and reserve is not None:
+            raise ValueError("substeps > 1 together with reserve is not available")
         n_scen, per_instance, params = self._plan_params(params)
         lead = (self.B,) if common else (self.B, n_scen)
         dur, level, reach = self._outputs(lead, (True, (), F8), (True, (self.N + 1,), I4), (want_reach, (2,), I4))
@@ -688,7 +707,9 @@ class BatchMPC:
         head = (self._h, n_scen, ptr(params), per_instance, int(speeds.size), ptr(speeds), _level_of(speeds, start, "start"), _level_of(speeds, end, "end"),
                 int(bool(common)), int(bool(boxes)))
         outs = (ptr(dur), iptr(level), iptr(reach), uptr(edges) if want_edges else None, iptr(iters))
-        if reserve is None:
+        if substeps != 1:
+            check(self._lib.upr_batch_retime_plan_substeps(*head, int(substeps), *outs))
+        elif reserve is None:
             check(self._lib.upr_batch_retime_plan(*head, *outs))
         else:
             if frame not in ("world", "tray", 0, 1):
@@ -722,6 +743,50 @@ class BatchMPC:
             q, v, a = xk[..., :nq], xk[..., nq:2 * nq], xk[..., 2 * nq:]
             return np.concatenate([q + 0.0 * sk[..., None], sk[..., None] * v, (sk * sk)[..., None] * a + d[..., None] * v], axis=-1)
         return t, side(x[..., :-1, :], s0), side(x[..., 1:, :], s1)
+
+    def retimed_substates(self, level, speeds, substeps):
+        """(t, x) of the time laws `level` (.., N + 1) of retime_plan on the current plan at the substep points of every segment, leading
+        axes as retimed_states': t (.., N, R + 1) = T_i + 2 tau_r / (s_i + s_r), tau_r = r dt / R; x (.., N, R + 1, 3 nq) the states
+        retime_plan(.., substeps=R) judges, (Q, s_r Q', s_r^2 Q'' + d_i Q') on the quintic Hermite path of replay_plan with s_r =
+        sqrt(((R - r) s_i^2 + r s_{i+1}^2) / R).  r = 0 is retimed_states' dep and r = R its arr, as doubles (the knot records are not
+        interpolated).  NaN where the plan has no time law (level -1).  Plain numpy."""
+        R = int(substeps)
+        if R < 1:
+            raise ValueError("substeps must be >= 1")
+        T, dep, arr = self.retimed_states(level, speeds)
+        speeds = np.asarray(speeds, dtype=np.float64).reshape(-1)
+        level = np.asarray(level)
+        _, xs, _ = self.solution()
+        nq, dt = self.problem.nq, float(self.problem.dt)
+        xk = xs[..., :3 * nq]
+        if level.ndim == 3:
+            xk = np.broadcast_to(xk[:, None], level.shape[:2] + xk.shape[1:])
+        s = np.where(level >= 0, speeds[np.maximum(level, 0)], np.nan)
+        s0, s1 = s[..., :-1], s[..., 1:]
+        d = (s1 - s0) * (s1 + s0) / (2.0 * dt)
+        x0, x1 = xk[..., :-1, :], xk[..., 1:, :]
+        c = [x0[..., :nq], dt * x0[..., nq:2 * nq], dt * dt * x0[..., 2 * nq:], x1[..., :nq], dt * x1[..., nq:2 * nq], dt * dt * x1[..., 2 * nq:]]
+        t = np.empty(s0.shape + (R + 1,))
+        x = np.empty(s0.shape + (R + 1, 3 * nq))
+        t[..., 0], x[..., 0, :] = T[..., :-1], dep
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t[..., R] = T[..., :-1] + 2.0 * dt / (s0 + s1)
+            x[..., R, :] = arr
+            for r in range(1, R):
+                tau, g = float(r) * dt / float(R), (float(r) * dt / float(R)) / dt
+                sr = np.sqrt((float(R - r) * (s0 * s0) + float(r) * (s1 * s1)) / float(R))
+                H = [1 - 10 * g**3 + 15 * g**4 - 6 * g**5, g - 6 * g**3 + 8 * g**4 - 3 * g**5, .5 * g**2 - 1.5 * g**3 + 1.5 * g**4 - .5 * g**5,
+                     10 * g**3 - 15 * g**4 + 6 * g**5, -4 * g**3 + 7 * g**4 - 3 * g**5, .5 * g**3 - g**4 + .5 * g**5]
+                D = [-30 * g**2 + 60 * g**3 - 30 * g**4, 1 - 18 * g**2 + 32 * g**3 - 15 * g**4, g - 4.5 * g**2 + 6 * g**3 - 2.5 * g**4,
+                     30 * g**2 - 60 * g**3 + 30 * g**4, -12 * g**2 + 28 * g**3 - 15 * g**4, 1.5 * g**2 - 4 * g**3 + 2.5 * g**4]
+                E = [-60 * g + 180 * g**2 - 120 * g**3, -36 * g + 96 * g**2 - 60 * g**3, 1 - 9 * g + 18 * g**2 - 10 * g**3,
+                     60 * g - 180 * g**2 + 120 * g**3, -24 * g + 84 * g**2 - 60 * g**3, 3 * g - 12 * g**2 + 10 * g**3]
+                Q0 = sum(w * v for w, v in zip(H, c))
+                Q1 = sum(w * v for w, v in zip(D, c)) / dt
+                Q2 = sum(w * v for w, v in zip(E, c)) / (dt * dt)
+                t[..., r] = T[..., :-1] + 2.0 * tau / (s0 + sr)
+                x[..., r, :] = np.concatenate([Q0 + 0.0 * sr[..., None], sr[..., None] * Q1, (sr * sr)[..., None] * Q2 + d[..., None] * Q1], axis=-1)
+        return t, x
 
     def replay_plan(self, level, speeds, tick, params=None, t0=0.0, n_samples=None, boxes=True, want_rho=False, want_iters=False, reductions=False):
         """(t, x, excess): the time law `level` of retime_plan replayed on a clock (upr_batch_replay_plan) -- the states a tracking
